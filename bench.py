@@ -2,7 +2,15 @@
 """Throughput benchmark of the batched BallEnv step (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--envs E] [--window 10]
+                    [--dump-outputs DIR] [--full]
     (N > 1: torchrun --nproc-per-node N ... bench.py --gpus N, one rank per GPU)
+
+A plain run does what the headline figure needs and no more: set up, warm up,
+time the K steps, write the last step's outputs (--dump-outputs) and print the
+result line.  --full adds everything else the benchmark measures -- the CPU
+baselines and the other legs (cold action rows, the eager drop-in, BASELINE
+configs 2 / 4 / 5, the 2^20-env batch, from-reset, createBoard, the fused
+rollouts, block counts) -- as further keys of the same line.
 
 A "step" = one be_step launch over the whole local batch: agent move, obstacle
 moves (Philox), collision, reward/done, TimeLimit(1000), in-kernel autoreset and
@@ -21,7 +29,7 @@ Kernel duration for the roofline: HIP events recorded on the replay stream
 around the timed region (K back-to-back be_kernel launches, nothing else on the
 stream) -> average per launch; it includes the small inter-launch gap, so it is
 an upper bound on the kernel duration that rocprofv3 reports.
-CPU baseline (rank 0, N=1 only, before any GPU work): oracle/py_ballenv.py,
+CPU baseline (--full; rank 0, N=1 only, before any GPU work): oracle/py_ballenv.py,
 the reference's algorithm restated in scalar Python, one process per core.
 """
 from __future__ import annotations
@@ -51,6 +59,14 @@ def parse():
     p.add_argument("--mode", choices=["loop", "graph", "eager"], default="graph",
                    help="loop: be_step_n, the K step launches queued by the library's C loop; graph: "
                         "hipGraph replay of captured be_step launches; eager: one ctypes be_step call per step")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline, also run everything else the benchmark measures: the CPU baselines "
+                        "and the other legs (cold action rows, eager step, configs 2/4/5, large batch, from reset, "
+                        "createBoard, fused rollouts, block counts), each sized by its own option below; without "
+                        "--full a run does the headline only and those options have no effect")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step returned (obs, reward, done and the "
+                        "info arrays of BatchedBallEnv.step) as DIR/<name>.npy, float32 / float64")
     p.add_argument("--cpu-seconds", type=float, default=12.0)
     p.add_argument("--cpu-procs", type=int, default=0, help="0 = one per usable host core")
     p.add_argument("--board-cpu-seconds", type=float, default=6.0,
@@ -938,6 +954,76 @@ def board_leg(args, gb, dev, rank, world, stream):
     return res
 
 
+DUMP_LIMIT = 64 << 20   # bytes --dump-outputs may write in all
+
+
+def dump_outputs(path, env, rank):
+    """--dump-outputs: what the last timed step returned to its caller -- the (obs, reward, done,
+    info) of BatchedBallEnv.step, i.e. the env's output buffers -- as <path>/<name>.npy, float32
+    (float64 for the f64 arrays); rank r > 0 writes <name>_rank<r>.npy.  Every input is seeded
+    (actions, resets and obstacle draws are Philox by global env id), so the same arguments give
+    the same arrays on every run.  A batch whose arrays exceed DUMP_LIMIT is cut to a fixed seeded
+    sample of envs, whose ids go to env_index.npy."""
+    import numpy as np
+    import torch
+    outs = {"obs": env.obs, "reward": env.reward, "done": env.done, "truncated": env.truncated,
+            "final_return": env.final_return, "final_len": env.final_len}
+    N = env.num_envs
+    per_env = sum((8 if t.dtype == torch.float64 else 4) * (t.numel() // N) for t in outs.values())
+    keep = None
+    if per_env * N > DUMP_LIMIT - 4096:
+        n = (DUMP_LIMIT - 4096) // (per_env + 8)      # 4 KB for the .npy headers; 8: the env id
+        keep = np.sort(np.random.default_rng(0xD0).choice(N, n, replace=False))
+        outs = {k: t[torch.from_numpy(keep).to(t.device)] for k, t in outs.items()}
+    os.makedirs(path, exist_ok=True)
+    suffix = f"_rank{rank}" if rank else ""
+    for k, t in outs.items():
+        a = t.cpu().numpy()
+        np.save(os.path.join(path, f"{k}{suffix}.npy"), a.astype(np.float64 if a.dtype == np.float64 else np.float32))
+    if keep is not None:
+        np.save(os.path.join(path, f"env_index{suffix}.npy"), keep.astype(np.float64))
+
+
+def full_legs(args, gb, env, lib, dev, rank, world, stream, B, kernel_us, base, board_base):
+    """--full: every leg beside the headline, in the result line's order (a leg whose step option is
+    0 is None).  env is the headline's env (cold_action_rows steps it on); base / board_base are the
+    CPU baselines taken before any GPU work, or None."""
+    cold_res = cold_actions_leg(args, env, lib, dev, stream, world, B) if args.cold_steps > 0 else None
+    eager_res = eager_step_leg(args, gb, dev, rank, world, stream, kernel_us) if args.eager_steps > 0 else None
+    c2_res = config2_leg(args, gb, dev, rank, world, stream) if args.config2_steps > 0 else None
+    c4_res = config4_leg(args, gb, dev, rank, world, stream) if args.config4_steps > 0 else None
+    large_res = large_batch_leg(args, gb, dev, rank, world, stream) if args.large_steps > 0 else None
+    fresh_res = from_reset_leg(args, gb, dev, rank, world, stream) if args.from_reset_steps > 0 else None
+    pol_res = policy_leg(args, gb, dev, rank, world, stream) if args.policy_steps > 0 else None
+    board_res = board_leg(args, gb, dev, rank, world, stream) if args.board_steps > 0 else None
+    if board_res is not None:
+        board_res["cpu_baseline"] = board_base
+    roll_res = rollout_leg(args, gb, dev, rank, world, stream) if args.rollout_steps > 0 else None
+    if roll_res is not None and world == 1:
+        # the same fused mode at the other BASELINE sizes (SURVEY 8(d) reports it separately): config 2
+        # (4 096 envs, W=5: rolloutw_kernel) and config 4's 8-GPU shard (32 768 envs at the last rank's ids)
+        from gym_ballenv_amd.distributed import shard
+        roll_res["config2"] = rollout_leg(args, gb, dev, 0, 1, stream, N=args.config2_envs, W=5, env_offset=0,
+                                          pmc_suffix="pmc_rollout_config2.json",
+                                          label=f"BASELINE config 2: random-action rollout, {args.config2_envs} envs, W=5")
+        off8, n8 = shard(262144, 7, 8)       # BASELINE config 4's batch, whatever --config4-envs says
+        roll_res["shard_32768"] = rollout_leg(args, gb, dev, 0, 1, stream, N=n8, W=10, env_offset=off8,
+                                              pmc_suffix=f"pmc_rollout_shard_{n8}.json",
+                                              label=f"config 4's 8-GPU shard: random-action rollout, {n8} envs "
+                                                    f"(global ids {off8}..{off8 + n8 - 1}), W=10")
+        if base is not None:   # the host port at the same windows (cpu_baseline.by_window)
+            for key, w in (("config2", 5), ("shard_32768", 10)):
+                bw = base["by_window"].get(f"W={w}")
+                if bw:
+                    roll_res[key]["cpu_baseline_ref"] = {"window": w, "aggregate": bw["aggregate"],
+                                                         "per_core": bw["per_core_mean"], "cores": base["cores"],
+                                                         "source": f"cpu_baseline.by_window.W={w}"}
+    blocks_res = blocks_leg(args, gb, dev, rank, world, stream) if args.blocks_launches > 0 else None
+    return {"cold_action_rows": cold_res, "eager_step": eager_res, "config2": c2_res, "config4": c4_res,
+            "large_batch": large_res, "from_reset": fresh_res, "policy_rollout": pol_res,
+            "board_profile": board_res, "fused_rollout": roll_res, "blocks_obs": blocks_res}
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -952,7 +1038,7 @@ def main():
                          f"torchrun --nproc-per-node {args.gpus} bench.py --gpus {args.gpus}, or bench.py --gpus N alone)")
 
     base = board_base = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         base = cpu_baseline(args.window, args.cpu_seconds, args.cpu_procs)
         if args.board_steps > 0 and args.board_cpu_seconds > 0:
             board_base = board_cpu_baseline(args.board_cpu_seconds, args.cpu_procs)
@@ -1098,37 +1184,11 @@ def main():
     pmc = newest_pmc("pmc_step_kernel.json", f"::{kname}(", N)
     traffic, traffic_src = (pmc["hbm_bytes_per_dispatch"], pmc["source"]) if pmc else (None, None)
 
-    cold_res = cold_actions_leg(args, env, lib, dev, stream, world, B) if args.cold_steps > 0 else None
-    eager_res = eager_step_leg(args, gb, dev, rank, world, stream, kern_ms * 1e3) if args.eager_steps > 0 else None
-    c2_res = config2_leg(args, gb, dev, rank, world, stream) if args.config2_steps > 0 else None
-    c4_res = config4_leg(args, gb, dev, rank, world, stream) if args.config4_steps > 0 else None
-    large_res = large_batch_leg(args, gb, dev, rank, world, stream) if args.large_steps > 0 else None
-    fresh_res = from_reset_leg(args, gb, dev, rank, world, stream) if args.from_reset_steps > 0 else None
-    pol_res = policy_leg(args, gb, dev, rank, world, stream) if args.policy_steps > 0 else None
-    board_res = board_leg(args, gb, dev, rank, world, stream) if args.board_steps > 0 else None
-    if board_res is not None:
-        board_res["cpu_baseline"] = board_base
-    roll_res = rollout_leg(args, gb, dev, rank, world, stream) if args.rollout_steps > 0 else None
-    if roll_res is not None and world == 1:
-        # the same fused mode at the other BASELINE sizes (SURVEY 8(d) reports it separately): config 2
-        # (4 096 envs, W=5: rolloutw_kernel) and config 4's 8-GPU shard (32 768 envs at the last rank's ids)
-        from gym_ballenv_amd.distributed import shard
-        roll_res["config2"] = rollout_leg(args, gb, dev, 0, 1, stream, N=args.config2_envs, W=5, env_offset=0,
-                                          pmc_suffix="pmc_rollout_config2.json",
-                                          label=f"BASELINE config 2: random-action rollout, {args.config2_envs} envs, W=5")
-        off8, n8 = shard(262144, 7, 8)       # BASELINE config 4's batch, whatever --config4-envs says
-        roll_res["shard_32768"] = rollout_leg(args, gb, dev, 0, 1, stream, N=n8, W=10, env_offset=off8,
-                                              pmc_suffix=f"pmc_rollout_shard_{n8}.json",
-                                              label=f"config 4's 8-GPU shard: random-action rollout, {n8} envs "
-                                                    f"(global ids {off8}..{off8 + n8 - 1}), W=10")
-        if base is not None:   # the host port at the same windows (cpu_baseline.by_window)
-            for key, w in (("config2", 5), ("shard_32768", 10)):
-                bw = base["by_window"].get(f"W={w}")
-                if bw:
-                    roll_res[key]["cpu_baseline_ref"] = {"window": w, "aggregate": bw["aggregate"],
-                                                         "per_core": bw["per_core_mean"], "cores": base["cores"],
-                                                         "source": f"cpu_baseline.by_window.W={w}"}
-    blocks_res = blocks_leg(args, gb, dev, rank, world, stream) if args.blocks_launches > 0 else None
+    if args.dump_outputs:
+        # before any other leg: cold_action_rows steps this env on
+        dump_outputs(args.dump_outputs, env, rank)
+    legs = full_legs(args, gb, env, lib, dev, rank, world, stream, B, kern_ms * 1e3, base, board_base) \
+        if args.full else {}
 
     if rank == 0:
         line = {
@@ -1154,19 +1214,10 @@ def main():
                          "measured_note": "measured_frac = PMC bytes per launch (2 x FETCH_SIZE + WRITE_SIZE) / kernel "
                                           "time / 8 TB/s; at 65 536 envs those bytes are Infinity-Cache (MALL) "
                                           "fabric requests, not DRAM: see large_batch for a DRAM-resident point"},
-            "cpu_baseline": base,
             "episodes": ep,
-            "cold_action_rows": cold_res,
-            "eager_step": eager_res,
-            "config2": c2_res,
-            "config4": c4_res,
-            "large_batch": large_res,
-            "from_reset": fresh_res,
-            "policy_rollout": pol_res,
-            "board_profile": board_res,
-            "fused_rollout": roll_res,
-            "blocks_obs": blocks_res,
         }
+        if args.full:
+            line.update({"cpu_baseline": base, **legs})
         moved(line["roofline"], B_eng, N, kern_ms * 1e3, pmc)
         if headline_pool:
             line["roofline"]["autoreset_pool"] = headline_pool

@@ -33,7 +33,7 @@ def test_board_cpu_baseline_leg_small_sample():
 
 @pytest.mark.gpu
 def test_bench_json_line(gpu):
-    cmd = [sys.executable, "bench.py", "--steps", "20", "--warmup", "5", "--settle", "60", "--no-cpu-baseline",
+    cmd = [sys.executable, "bench.py", "--full", "--steps", "20", "--warmup", "5", "--settle", "60", "--no-cpu-baseline",
            "--policy-steps", "20", "--torch-policy-steps", "5", "--board-steps", "20", "--rollout-steps", "100",
            "--config2-steps", "50", "--config4-steps", "20", "--large-steps", "20", "--from-reset-steps", "20",
            "--blocks-launches", "8", "--eager-steps", "50", "--shard-steps", "20"]
@@ -166,6 +166,80 @@ def _bench_line(args, timeout=110):
     return json.loads(lines[0])
 
 
+_LEG_KEYS = ("cpu_baseline", "cold_action_rows", "eager_step", "config2", "config4", "large_batch", "from_reset",
+             "policy_rollout", "board_profile", "fused_rollout", "blocks_obs")
+
+
+def test_dump_outputs_sample(tmp_path, monkeypatch):
+    """--dump-outputs keeps within its byte limit: a batch past it is cut to a fixed seeded sample of
+    envs (the same rows of every array, ids in env_index.npy); a batch within it is written whole."""
+    import types
+    import numpy as np
+    import torch
+    import bench
+    N, F = 1000, 104
+    g = torch.Generator().manual_seed(1)
+    env = types.SimpleNamespace(
+        num_envs=N, obs=torch.randint(0, 2, (N, F), dtype=torch.uint8, generator=g),
+        reward=torch.rand(N, dtype=torch.float64, generator=g), done=torch.rand(N, generator=g) < 0.1,
+        truncated=torch.rand(N, generator=g) < 0.1, final_return=torch.rand(N, dtype=torch.float64, generator=g),
+        final_len=torch.randint(0, 1000, (N,), dtype=torch.int32, generator=g))
+    names = ("obs", "reward", "done", "truncated", "final_return", "final_len")
+    bench.dump_outputs(str(tmp_path / "whole"), env, 0)
+    assert sorted(os.listdir(tmp_path / "whole")) == sorted(n + ".npy" for n in names)
+    for n in names:
+        a = np.load(tmp_path / "whole" / (n + ".npy"))
+        want = np.float64 if getattr(env, n).dtype == torch.float64 else np.float32
+        assert a.dtype == want and np.array_equal(a, getattr(env, n).numpy().astype(want)), n
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 100_000)
+    for d in ("cut", "again"):
+        bench.dump_outputs(str(tmp_path / d), env, 0)
+    files = os.listdir(tmp_path / "cut")
+    assert sum(os.path.getsize(tmp_path / "cut" / f) for f in files) <= 100_000
+    idx = np.load(tmp_path / "cut" / "env_index.npy")
+    assert idx.dtype == np.float64 and 100 < len(idx) < N and np.all(np.diff(idx) > 0)
+    for n in names:
+        a = np.load(tmp_path / "cut" / (n + ".npy"))
+        assert np.array_equal(a, getattr(env, n).numpy()[idx.astype(np.int64)].astype(a.dtype)), n
+        assert np.array_equal(a, np.load(tmp_path / "again" / (n + ".npy"))), n
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_last_step(gpu, tmp_path):
+    """A plain run (no --full) times the headline only -- none of the other legs' keys, --steps
+    timed steps -- and --dump-outputs writes what the last timed step returned: the arrays equal
+    those of the same steps driven through BatchedBallEnv.step here (same seeds, same action rows,
+    same order: warm-up rows K.., untimed passes of rows 0..K-1 up to --settle, the timed pass)."""
+    import numpy as np
+    import gym_ballenv_amd as gb
+    N, K, WU, settle = 4096, 20, 5, 60
+    d = _bench_line(["--gpus", "1", "--envs", str(N), "--steps", str(K), "--warmup", str(WU), "--settle", str(settle),
+                     "--dump-outputs", str(tmp_path)])
+    assert not [k for k in _LEG_KEYS if k in d]
+    base = json.load(open(os.path.join(ROOT, "BASELINE.json")))
+    assert d["metric"] == base["metric"] and d["unit"] == "env-steps/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "int16x2+f64" and d["steps"] == K and d["warmup"] == WU and d["untimed_steps"] == 65
+    assert d["ms_per_step"] > 0 and d["value"] == pytest.approx(N * 1e3 / d["ms_per_step"], rel=1e-9)
+    assert d["roofline"]["kernel"] == "step2_kernel<10, 13, 5, true>" and d["episodes"]["episodes"] >= 0
+    env = gb.BatchedBallEnv(N, 10, gb.EnvConfig(), device=gpu, seed=0xBA11)
+    acts = env.sample_actions(K + WU, seed=0xBA11)
+    env.reset()
+    for t in range(WU):
+        env.step(acts[K + t])
+    for _ in range(4):                      # 3 untimed passes (5 + 3 x 20 >= 60) and the timed one
+        for t in range(K):
+            obs, reward, done, info = env.step(acts[t])
+    want = {"obs": obs, "reward": reward, "done": done, "truncated": info["truncated"],
+            "final_return": info["final_return"], "final_len": info["final_len"]}
+    assert sorted(os.listdir(tmp_path)) == sorted(n + ".npy" for n in want)
+    for n, t in want.items():
+        a = np.load(tmp_path / (n + ".npy"))
+        assert a.dtype == (np.float64 if n in ("reward", "final_return") else np.float32), n
+        assert a.shape == tuple(t.shape) and np.array_equal(a, t.cpu().numpy().astype(a.dtype)), n
+    assert want["obs"].any() and (want["reward"] != 0).any()
+    env.close()
+
+
 def test_bench_gpus_mismatch_refused():
     """--gpus N inside a launch of another world size fails loudly (no silent one-rank run)."""
     env = dict(os.environ, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")
@@ -210,7 +284,7 @@ def test_bench_config4_split_gloo(gpu):
     whole batch (the same global ids, so the same trajectories)."""
     only_c4 = [a for a in _ONLY_HEADLINE]
     only_c4[only_c4.index("--config4-steps") + 1] = "20"
-    common = ["--steps", "5", "--warmup", "2", "--settle", "60", "--envs", "4096", *only_c4]
+    common = ["--full", "--steps", "5", "--warmup", "2", "--settle", "60", "--envs", "4096", *only_c4]
     d2 = _bench_line(["--gpus", "2", "--dist-backend", "gloo", *common], timeout=200)
     d1 = _bench_line(["--gpus", "1", *common], timeout=200)
     c2, c1 = d2["config4"], d1["config4"]
@@ -240,7 +314,7 @@ def test_bench_rccl_one_rank(gpu):
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr=127.0.0.1",
-           f"--master-port={port}", "bench.py", "--gpus", "1", "--dist-backend", "nccl", "--steps", "20", "--warmup", "5",
+           f"--master-port={port}", "bench.py", "--gpus", "1", "--full", "--dist-backend", "nccl", "--steps", "20", "--warmup", "5",
            "--settle", "60", "--rollout-steps", "100", "--policy-steps", "20", "--torch-policy-steps", "0",
            "--board-steps", "20", "--cold-steps", "0", "--config2-steps", "20", "--config4-steps", "20",
            "--large-steps", "0",

@@ -13,9 +13,9 @@ set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 O=gpurun_out/${TAG:-ab}; mkdir -p $O
 if [ "${LEG:-step}" = board ]; then
-  ARGS="--no-cpu-baseline --steps 50 --warmup 10 --policy-steps 0 --torch-policy-steps 0 --board-steps 1000 --rollout-steps 0 --cold-steps 0 --config2-steps 0 --config4-steps 0 --large-steps 0 --from-reset-steps 0 --blocks-launches 0 --shard-steps 0 --eager-steps 0 ${EXTRA:-}"
+  ARGS="--full --no-cpu-baseline --steps 50 --warmup 10 --policy-steps 0 --torch-policy-steps 0 --board-steps 1000 --rollout-steps 0 --cold-steps 0 --config2-steps 0 --config4-steps 0 --large-steps 0 --from-reset-steps 0 --blocks-launches 0 --shard-steps 0 --eager-steps 0 ${EXTRA:-}"
 else
-  ARGS="--no-cpu-baseline --steps 1000 --warmup 100 --policy-steps 0 --torch-policy-steps 0 --board-steps 0 --rollout-steps 0 --cold-steps 0 --config2-steps 1000 --config4-steps 1000 --config4-envs ${ENVS4:-32768} --large-steps 0 --from-reset-steps 0 --blocks-launches 0 --shard-steps 0 --eager-steps 0 ${EXTRA:-}"
+  ARGS="--full --no-cpu-baseline --steps 1000 --warmup 100 --policy-steps 0 --torch-policy-steps 0 --board-steps 0 --rollout-steps 0 --cold-steps 0 --config2-steps 1000 --config4-steps 1000 --config4-envs ${ENVS4:-32768} --large-steps 0 --from-reset-steps 0 --blocks-launches 0 --shard-steps 0 --eager-steps 0 ${EXTRA:-}"
 fi
 for r in $(seq 1 ${REPS:-3}); do
   for v in ${ARMS:?ARMS}; do

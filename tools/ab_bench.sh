@@ -5,7 +5,7 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out/ab; export TMPDIR=/tmp
-ARGS="--no-cpu-baseline --steps ${STEPS:-1000} --warmup 100 --policy-steps 0 --board-steps 0 --rollout-steps 0 ${BENCH_ARGS:-}"
+ARGS="--full --no-cpu-baseline --steps ${STEPS:-1000} --warmup 100 --policy-steps 0 --board-steps 0 --rollout-steps 0 ${BENCH_ARGS:-}"
 for spec in "$@"; do
   IFS=@ read -r name lib envset <<< "$spec"
   envs=(); [ -n "$lib" ] && envs+=("BALLENV_LIB=$lib"); [ -n "$envset" ] && envs+=("$envset")

@@ -11,5 +11,5 @@ for v in ${VARIANTS:-base}; do
       --lanes ${LANES:-2} --reps ${REPS:-2} ${SWEEP_ARGS:-} > $O/sweep_${TAG:-w${W:-10}}_$v.jsonl 2>&1 || exit $?
 done
 if [ "${BENCH:-0}" = "1" ]; then
-  timeout -k 10 400 python -u bench.py > $O/bench.json 2> $O/bench.err || exit $?
+  timeout -k 10 400 python -u bench.py --full > $O/bench.json 2> $O/bench.err || exit $?
 fi

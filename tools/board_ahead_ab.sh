@@ -5,7 +5,7 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 O=gpurun_out/board_ahead_ab; mkdir -p $O
-ARGS="--no-cpu-baseline --steps 10 --warmup 2 --policy-steps 0 --torch-policy-steps 0 --rollout-steps 0 --board-steps 1000 --cold-steps 0 --config2-steps 0 --config4-steps 0 --large-steps 0 --from-reset-steps 0 --blocks-launches 0"
+ARGS="--full --no-cpu-baseline --steps 10 --warmup 2 --policy-steps 0 --torch-policy-steps 0 --rollout-steps 0 --board-steps 1000 --cold-steps 0 --config2-steps 0 --config4-steps 0 --large-steps 0 --from-reset-steps 0 --blocks-launches 0"
 for r in $(seq 1 ${REPS:-3}); do
   for spec in ${SPECS:-new:-:1 off:-:0}; do
     IFS=: read -r v lib ra <<< "$spec"

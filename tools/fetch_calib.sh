@@ -5,7 +5,7 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 O=gpurun_out/fetch_calib; mkdir -p $O; export TMPDIR=/tmp
-C2="--no-cpu-baseline --steps 10 --warmup 2 --settle 10 --policy-steps 0 --torch-policy-steps 0 --board-steps 0 --rollout-steps 0 --cold-steps 0 --config2-steps 200 --config4-steps 0 --large-steps 0 --from-reset-steps 0 --blocks-launches 0"
+C2="--full --no-cpu-baseline --steps 10 --warmup 2 --settle 10 --policy-steps 0 --torch-policy-steps 0 --board-steps 0 --rollout-steps 0 --cold-steps 0 --config2-steps 200 --config4-steps 0 --large-steps 0 --from-reset-steps 0 --blocks-launches 0"
 for c in FETCH_SIZE WRITE_SIZE "TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum"; do
   n=${c%% *}
   for mode in 0 1 2 3 4 5 6 7; do

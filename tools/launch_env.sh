@@ -9,10 +9,10 @@ for spec in ${SPECS:-default: batch1:DEBUG_HIP_GRAPH_BATCH_SIZE=1 batch4:DEBUG_H
   o=gpurun_out/launch_env/$name
   env $vars timeout -k 10 120 python3 tools/sync_cost.py > $o.sync.txt 2>&1
   rc=$?; echo "[$name] sync_cost rc=$rc"; [ $rc -ne 0 ] && { tail -5 $o.sync.txt; exit $rc; }
-  env $vars timeout -k 10 200 python3 bench.py --no-cpu-baseline --steps 20 --warmup 5 --policy-steps 0 --board-steps 0 \
+  env $vars timeout -k 10 200 python3 bench.py --full --no-cpu-baseline --steps 20 --warmup 5 --policy-steps 0 --board-steps 0 \
       --rollout-steps 0 > $o.b20.log 2>&1
   rc=$?; [ $rc -ne 0 ] && { echo "[$name] b20 rc=$rc"; tail -5 $o.b20.log; exit $rc; }
-  env $vars timeout -k 10 200 python3 bench.py --no-cpu-baseline --steps 1000 --warmup 100 --policy-steps 0 \
+  env $vars timeout -k 10 200 python3 bench.py --full --no-cpu-baseline --steps 1000 --warmup 100 --policy-steps 0 \
       --board-steps 0 --rollout-steps 1000 > $o.b1000.log 2>&1
   rc=$?; [ $rc -ne 0 ] && { echo "[$name] b1000 rc=$rc"; tail -5 $o.b1000.log; exit $rc; }
   python3 - "$name" "$o" <<'EOF'

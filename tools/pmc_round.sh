@@ -12,7 +12,7 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 R=${ROUND:-r06}; O=gpurun_out/${R}_pmcr; mkdir -p $O
-PASSES="FETCH_SIZE WRITE_SIZE" timeout -k 10 500 bash tools/pmc_passes.sh ${R}_pmcr/p --no-cpu-baseline --steps 200 \
+PASSES="FETCH_SIZE WRITE_SIZE" timeout -k 10 500 bash tools/pmc_passes.sh ${R}_pmcr/p --full --no-cpu-baseline --steps 200 \
     --warmup 20 --settle 10 --policy-steps 0 --torch-policy-steps 0 --board-steps 0 --rollout-steps 200 --rollout-chunk 100 \
     --cold-steps 0 --config2-steps 200 --config4-steps 200 --config4-envs 32768 --large-steps 0 --from-reset-steps 0 \
     --blocks-launches 0 --shard-steps 0 --eager-steps 0 || exit 1

@@ -5,7 +5,7 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 O=gpurun_out/rev_ab; mkdir -p $O
-ARGS="--no-cpu-baseline --steps 1000 --warmup 100 --policy-steps 1000 --torch-policy-steps 0 --board-steps 1000 \
+ARGS="--full --no-cpu-baseline --steps 1000 --warmup 100 --policy-steps 1000 --torch-policy-steps 0 --board-steps 1000 \
   --rollout-steps 1000 --cold-steps 0 --config2-steps 1000 --config4-steps 0 --large-steps 0 --from-reset-steps 0 --blocks-launches 0"
 for r in $(seq 1 ${REPS:-2}); do
   for v in new ${B}; do

@@ -4,7 +4,7 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out/short; export TMPDIR=/tmp
-LEGS="--no-cpu-baseline --policy-steps 0 --board-steps 0 --rollout-steps 0"
+LEGS="--full --no-cpu-baseline --policy-steps 0 --board-steps 0 --rollout-steps 0"
 for mode in ${MODES:-graph loop}; do
   for sw in "20 5" "1000 100"; do
     set -- $sw

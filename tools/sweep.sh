@@ -6,7 +6,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out; : > gpurun_out/sweep.jsonl
 for spec in ${SIZES:-4096:5 65536:10 262144:10 1048576:10}; do   # envs:window
   set -- ${spec/:/ }
-  timeout -k 10 300 python3 bench.py --no-cpu-baseline --envs $1 --window $2 --steps 1000 --warmup 100 --policy-steps 0 \
+  timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --envs $1 --window $2 --steps 1000 --warmup 100 --policy-steps 0 \
       --board-steps 0 --rollout-steps 1000 > gpurun_out/sweep_$1.log 2>&1
   rc=$?; [ $rc -ne 0 ] && { echo "envs $1 rc=$rc"; tail -5 gpurun_out/sweep_$1.log; exit $rc; }
   tail -1 gpurun_out/sweep_$1.log >> gpurun_out/sweep.jsonl

@@ -1,5 +1,5 @@
 """Per-region kernel averages from a rocprofv3 kernel trace (run_kernel_trace.csv) of the default
-`python3 bench.py` command: the headline's timed region, config 2's, config 4's and the 2^20-env leg's.
+`python3 bench.py --full` command: the headline's timed region, config 2's, config 4's and the 2^20-env leg's.
 
     python tools/trace_regions.py <kernel_trace.csv> [--warmup 100] [--untimed 1000] [--steps 1000]
 
