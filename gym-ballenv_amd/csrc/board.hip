@@ -19,9 +19,9 @@
 // Every coordinate is f64 as in the reference (ranf spawns; the actions are the integer
 // actionArray moves or arbitrary float deltas).  Distances are sqrt(fl(x*x) + fl(y*y)) --
 // math.sqrt(math.pow(x, 2) + math.pow(y, 2)) with correctly rounded pow(x, 2) and sqrt, no
-// FMA contraction -- so positions, rewards, returns and done are bit-exact.  The features
-// use hypot / acos / exp (1-ulp libraries on both sides): their bins and counts are exact
-// away from measure-zero boundaries and the social-force sum agrees to ~1e-16 relative.
+// FMA contraction -- so positions, rewards, returns and done are bit-exact.  The features'
+// bins and counts are exact, at their cuts too (features() below; tests/test_board_edges.py),
+// and the social-force sum (exp, a 1-ulp library on both sides) agrees to ~1e-16 relative.
 //
 // createBoard's velocities are identically zero (the agent's agent_x_vel is never changed,
 // :338; Obstacle vel defaults to 0, :40-47), so for every obstacle relvel = 0 -> speed bin 0
@@ -179,16 +179,41 @@ __device__ void features(const BParams& p, float4* out, double ax, double ay, do
   const double nv = sqrt(__dadd_rn(__dmul_rn(vx, vx), __dmul_rn(vy, vy)));   // |goal - agent|
   // calcDistanceFromGoal (:132-144): floor(hypot(ax - gx, ay - gy) / 5), capped at 5.  nv is the
   // same length (correctly rounded sqrt of the rounded sum; within a few ulps of hypot's 1-ulp
-  // result), so floor(nv / 5) is floor(hypot / 5) unless nv / 5 lies within 1e-9 of an integer:
-  // only a wave with such a lane (never seen in practice) evaluates hypot.
+  // result), so floor(nv / 5) is floor(hypot / 5) unless nv / 5 lies within 1e-9 of an integer.
+  // Random f64 states never are; a goal numerically on a circle of radius 5 .. 30 is, and there
+  // the last bit of the reference's np.hypot decides (tests/test_board_edges.py runs those lanes:
+  // the device hypot flipped 58 of 741 of them).  np.hypot is the host libm's: glibc 2.35's, nv
+  // corrected once by the residual of its square (Borges, "An improved algorithm for hypot(a, b)",
+  // 2019), every operation rounded on its own -- restated here, so the lane follows it bit for bit.
   const double tq = nv / 5.0, tf = floor(tq);
   double dg = tf;
-  if (tq - tf < 1e-9 || tf + 1.0 - tq < 1e-9)
-    dg = floor(hypot(ax - gx, ay - gy) / 5.0);
+  if (tq - tf < 1e-9 || tf + 1.0 - tq < 1e-9) {
+    const double hx = fmax(fabs(vx), fabs(vy)), hy = fmin(fabs(vx), fabs(vy));
+    double hc = __dadd_rn(hx, hy);   // hy below half an ulp of hx: hypot returns the sum
+    if (hy > hx * 0x1p-54) {
+      const double h2 = __dmul_rn(2.0, nv);
+      double t1, t2;
+      if (nv <= __dmul_rn(2.0, hy)) {
+        const double d = __dsub_rn(nv, hy);
+        t1 = __dmul_rn(hx, __dsub_rn(__dmul_rn(2.0, d), hx));
+        t2 = __dmul_rn(__dsub_rn(d, __dmul_rn(2.0, __dsub_rn(hx, hy))), d);
+      } else {
+        const double d = __dsub_rn(nv, hx);
+        t1 = __dmul_rn(__dmul_rn(2.0, d), __dsub_rn(hx, __dmul_rn(2.0, hy)));
+        t2 = __dadd_rn(__dmul_rn(__dsub_rn(__dmul_rn(4.0, d), hy), hy), __dmul_rn(d, d));
+      }
+      hc = __dsub_rn(nv, __ddiv_rn(__dadd_rn(t1, t2), h2));
+    }
+    dg = floor(hc / 5.0);
+  }
   f[0] = (float)(dg > 5.0 ? 5.0 : dg);
   // relativeGoalPos (:146-166): angle between (0, 1) and (gx - ax, gy - ay), acos(c) of the
   // clipped cosine c.  acos decreases, so ang < pi/4 is c > cos(pi/4) and ang > 3 pi/4 is
-  // c < -cos(pi/4); acos (1 ulp) only decides a lane within 1e-9 of those cuts.
+  // c < -cos(pi/4), away from those cuts.  Within 1e-9 of them the reference's arccos (glibc) decides,
+  // and the doubles at which it changes sides are few (tests/golden/board_edges.npz, group 2: 2 680
+  // exact diagonals and their ulp neighbours): arccos(c) < fl(pi/4) for c > KP, == fl(pi/4) at
+  // c == KP = fl(sqrt(1/2)) -- neither strict test passes: "behind" -- and > fl(pi/4) below;
+  // arccos(c) < fl(3 pi/4) for c > KN, which lies two ulps inside -KP.  No library call decides.
   double c = nv > 0.0 ? vy / nv : 0.0;
   c = c < -1.0 ? -1.0 : (c > 1.0 ? 1.0 : c);
   constexpr double COS_PI4 = 0.70710678118654752;
@@ -196,8 +221,8 @@ __device__ void features(const BParams& p, float4* out, double ax, double ay, do
   bin = c > COS_PI4 ? 0 : (c > -COS_PI4 ? 1 : 2);
   if (fabs(fabs(c) - COS_PI4) < 1e-9)
   {
-    const double ang = acos(c);
-    bin = ang < PI / 4 ? 0 : ((ang > PI / 4 && ang < PI * 3 / 4) ? 1 : 2);
+    constexpr double KP = 0x1.6a09e667f3bcdp-1, KN = -0x1.6a09e667f3bcbp-1;
+    bin = c > KP ? 0 : (c == KP ? 2 : (c > KN ? 1 : 2));
   }
   if (bin == 0) f[1] = 1.f;
   else if (bin == 1) { if (vx > 0) f[2] = 1.f; else f[4] = 1.f; }

@@ -60,6 +60,12 @@ static void board_features(const be_board_config* c, const be_board_state* st, i
   }
 }
 
+/* featureExtractor on the state as it stands (be_board_observe): tests/test_board_edges.py */
+int orc_board_observe(const be_board_config* c, const be_board_state* st, float* features) {
+  for (int32_t i = 0; i < c->num_envs; ++i) board_features(c, st, i, features + (int64_t)i * 20);
+  return 0;
+}
+
 /* createBoard.reset (:460-513) from a (len, N) f64 tape; returns 0 or a BE_STATUS bit */
 int orc_board_reset(const be_board_config* c, const be_board_state* st, const double* tape, int32_t len,
                     float* features) {

@@ -47,6 +47,7 @@ def lib():
         L.orc_board_reset.argtypes = [vp, vp, vp, i32, vp]
         L.orc_board_step.argtypes = [vp, vp, vp, vp, vp, vp, vp]
         L.orc_board_reset_philox.argtypes = [vp, vp, vp, vp]
+        L.orc_board_observe.argtypes = [vp, vp, vp]
         _lib = L
     return _lib
 
@@ -168,6 +169,13 @@ def board_reset_philox(cfg, st, mask=None):
     f = np.zeros((cfg.num_envs, 20), np.float32)
     s = lib().orc_board_reset_philox(C.byref(cfg), C.byref(_board_struct(st)), _p(m), _p(f))
     return s, f
+
+
+def board_observe(cfg, st):
+    """featureExtractor on the state as it stands; returns features (N, 20) f32."""
+    f = np.zeros((cfg.num_envs, 20), np.float32)
+    lib().orc_board_observe(C.byref(cfg), C.byref(_board_struct(st)), _p(f))
+    return f
 
 
 def board_step(cfg, st, actions=None, deltas=None):
