@@ -31,6 +31,7 @@ EXPORTS = ("be_abi_version", "be_config_default", "be_config_check", "be_step_by
            "be_board_config_default", "be_board_create", "be_board_destroy", "be_board_last_error",
            "be_board_reset", "be_board_step", "be_board_rollout", "be_board_observe", "be_board_status",
            "be_board_pool_bytes")
+# be_a2c_targets is declared and exported too; the loader below checks it by name like the rest (sig)
 BOARD_MAX_STATIC, BOARD_MAX_ACTIONS, BOARD_FEATURES = 32, 16, 20
 
 
@@ -67,6 +68,11 @@ class BeOut(C.Structure):
 
 class BeActOut(C.Structure):
     _fields_ = [("action", C.c_void_p), ("log_prob", C.c_void_p), ("value", C.c_void_p), ("probs", C.c_void_p)]
+
+
+class BeA2COut(C.Structure):
+    _fields_ = [("returns", C.c_void_p), ("returns_norm", C.c_void_p), ("advantage", C.c_void_p),
+                ("valid", C.c_void_p)]
 
 
 class BeBoardConfig(C.Structure):
@@ -145,6 +151,7 @@ def lib() -> C.CDLL:
         "be_policy_rollout": (C.c_int, [vp, P(BeState), vp, vp, i32, P(BeOut), P(BeActOut), u64, vp]),
         "be_policy_bytes": (i64, [vp]),
         "be_observe_blocks": (C.c_int, [vp, P(BeState), vp, vp, vp]),
+        "be_a2c_targets": (C.c_int, [vp, vp, vp, vp, vp, i32, C.c_double, C.c_double, P(BeA2COut), vp]),
         "be_board_config_default": (C.c_int, [P(BeBoardConfig), i32, i32]),
         "be_board_create": (C.c_int, [P(BeBoardConfig), i32, P(vp)]),
         "be_board_destroy": (C.c_int, [vp]),

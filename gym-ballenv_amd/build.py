@@ -2,13 +2,14 @@
 
     python -m gym_ballenv_amd.build [--force]
 
-Two translation units, compiled separately (each embeds its own gfx950 code
+Translation units, compiled separately (each embeds its own gfx950 code
 object) and linked into one shared library:
   csrc/ballenv.hip  step / reset / observe kernels + the C ABI
   csrc/policy.hip   select_action kernel (-fno-slp-vectorize: scalar f32 FMAs
                     interleave better with MFMAs than SLP-packed ones on gfx950)
   csrc/features.hip sibling observation formats (prep_state2 block counts)
   csrc/board.hip    the createBoard physics profile + featureExtractor
+  csrc/a2c.hip      A2C targets of a recorded rollout (the batched finish_episode)
 """
 from __future__ import annotations
 
@@ -29,7 +30,8 @@ BASE_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math
 # tiles' accumulators in AGPRs, which costs 12 v_accvgpr_read per tile row (of ~70 VALU); only
 # the kernels with MFMAs (the policy forward and the fused policy rollouts) change.
 VGPR_MFMA = ["-mllvm", "-amdgpu-mfma-vgpr-form"]
-UNITS = {"ballenv.hip": VGPR_MFMA, "policy.hip": ["-fno-slp-vectorize", *VGPR_MFMA], "features.hip": [], "board.hip": []}
+UNITS = {"ballenv.hip": VGPR_MFMA, "policy.hip": ["-fno-slp-vectorize", *VGPR_MFMA], "features.hip": [], "board.hip": [],
+         "a2c.hip": []}
 HEADERS = [HDR, *(os.path.join(CSRC, h) for h in ("philox.h", "internal.h", "policy_core.h", "diag.h"))]
 
 

@@ -31,12 +31,65 @@ training loop is rollout (HIP) -> update (torch autograd) -> re-pack (HIP).
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
 from . import _abi
 from .policy import HipPolicy, Policy, torch_select_action
+
+
+class A2CTargets(NamedTuple):
+    """What ``a2c_targets`` returns, each (T, N) on the env's device."""
+    returns_norm: torch.Tensor              # f32 per-episode normalised return R^
+    advantage: Optional[torch.Tensor]       # f32 R^ - values (None without values)
+    valid: torch.Tensor                     # u8 1: the element's episode has >= 2 steps
+    returns: Optional[torch.Tensor]         # f64 discounted return R
+
+
+def a2c_targets(env, rewards: torch.Tensor, dones: torch.Tensor, values: Optional[torch.Tensor] = None,
+                gamma: float = 0.99, eps: Optional[float] = None, bootstrap: Optional[torch.Tensor] = None,
+                with_returns: bool = True) -> A2CTargets:
+    """The targets of the batched ``finish_episode`` in one HIP kernel (``be_a2c_targets``).
+
+    rewards (T, N) f64, dones (T, N) bool or u8 0/1, values (T, N) f32 or None, bootstrap (N) f64
+    or None, all contiguous on ``env``'s device (N = env.num_envs).  The arithmetic is the one
+    include/ballenv.h pins, so two calls on the same inputs agree bit for bit and ``returns``
+    equals ``Rollout.discounted_returns``.  eps=None: fp32 eps, as in ``a2c_losses``.
+    Asynchronous on the caller's current stream; with_returns=False skips the f64 output."""
+    import numpy as np
+    eps = float(np.finfo(np.float32).eps) if eps is None else float(eps)
+    dev, N = env.device, env.num_envs
+    if rewards.dim() != 2 or rewards.shape[1] != N or rewards.shape[0] < 1 or rewards.dtype != torch.float64 or \
+            not rewards.is_contiguous() or rewards.device != dev:
+        raise ValueError("rewards must be a (T, N) contiguous f64 tensor on the env's device")
+    T = rewards.shape[0]
+    if dones.dtype not in (torch.bool, torch.uint8) or tuple(dones.shape) != (T, N) or not dones.is_contiguous() or \
+            dones.device != dev:
+        raise ValueError("dones must be a (T, N) contiguous bool / u8 tensor on the env's device")
+    if values is not None and (values.dtype != torch.float32 or tuple(values.shape) != (T, N) or
+                               not values.is_contiguous() or values.device != dev):
+        raise ValueError("values must be a (T, N) contiguous f32 tensor on the env's device")
+    if bootstrap is not None and (bootstrap.dtype != torch.float64 or tuple(bootstrap.shape) != (N,) or
+                                  not bootstrap.is_contiguous() or bootstrap.device != dev):
+        raise ValueError("bootstrap must be an (N) contiguous f64 tensor on the env's device")
+    rn = torch.empty(T, N, dtype=torch.float32, device=dev)
+    adv = torch.empty(T, N, dtype=torch.float32, device=dev) if values is not None else None
+    valid = torch.empty(T, N, dtype=torch.uint8, device=dev)
+    ret = torch.empty(T, N, dtype=torch.float64, device=dev) if with_returns else None
+    return a2c_targets_into(env, rewards, dones, values, gamma, eps, bootstrap, A2CTargets(rn, adv, valid, ret))
+
+
+def a2c_targets_into(env, rewards, dones, values, gamma: float, eps: float, bootstrap, out: A2CTargets) -> A2CTargets:
+    """``a2c_targets`` into tensors the caller allocated (no allocation: usable under graph capture).
+    The caller vouches for dtypes, shapes, contiguity and devices."""
+    ptr = lambda x: None if x is None else x.data_ptr()
+    o = _abi.BeA2COut(ptr(out.returns), ptr(out.returns_norm), ptr(out.advantage), ptr(out.valid))
+    rc = _abi.lib().be_a2c_targets(env._ctx, rewards.data_ptr(), dones.data_ptr(), ptr(values), ptr(bootstrap),
+                                   int(rewards.shape[0]), float(gamma), float(eps), C.byref(o), env._stream())
+    if rc:
+        _abi.check(rc, env._ctx)
+    return out
 
 
 class Rollout:
@@ -174,28 +227,19 @@ class Rollout:
             out[t] = R
         return out
 
+    def targets(self, gamma: float = 0.99, bootstrap: Optional[torch.Tensor] = None,
+                with_returns: bool = True) -> A2CTargets:
+        """``a2c_targets`` of this rollout's rewards, dones and values (one HIP kernel)."""
+        return a2c_targets(self.env, self.rewards, self.dones, self.values, gamma, None, bootstrap, with_returns)
+
     def close(self) -> None:
         self._graphs = []
         if self.hp is not None:
             self.hp.close()
 
 
-def a2c_losses(policy: Policy, obs: torch.Tensor, actions: torch.Tensor, rewards: torch.Tensor,
-               dones: torch.Tensor, gamma: float = 0.99, eps: Optional[float] = None):
-    """Batched ``finish_episode`` (examples/ball_cnn_ac3.py:222-246) over a recorded rollout.
-
-    obs (T, N, F) u8 -- the obs each action was chosen from; actions (T, N); rewards (T, N)
-    f64; dones (T, N) bool.  Every maximal run of an env's steps that ends at a done (or at
-    the horizon) is one episode, as ``policy.rewards`` / ``policy.saved_actions`` are in the
-    reference.  Per episode, exactly as there:
-      R_t = r_t + gamma R_{t+1} (python floats), then torch.tensor(R) (fp32),
-      R^ = (R - R.mean()) / (R.std() + eps)          (unbiased std, eps = fp32 eps),
-      policy loss  sum_t -log pi(a_t|s_t) * (R^_t - v_t.item()),
-      value loss   sum_t smooth_l1(v_t, R^_t).
-    Episodes of one step are skipped (the driver only trains when t > 0, :614).
-    log pi and v are recomputed from ``obs`` with autograd (the rollout's own values are
-    the same forward, taken without a graph).  Returns (policy_loss, value_loss) sums.
-    """
+def _torch_targets(rewards: torch.Tensor, dones: torch.Tensor, gamma: float = 0.99, eps: Optional[float] = None):
+    """The per-episode normalised returns of ``a2c_losses`` in plain torch: (Rn, valid), flat (T*N)."""
     import numpy as np
     eps = float(np.finfo(np.float32).eps) if eps is None else eps
     T, N = rewards.shape
@@ -218,6 +262,37 @@ def a2c_losses(policy: Policy, obs: torch.Tensor, actions: torch.Tensor, rewards
     var = torch.zeros(S, device=dev).index_add_(0, sid, dev2) / (cnt - 1).clamp(min=1)
     valid = (cnt > 1)[sid]
     Rn = (flat - mean[sid]) / (var.sqrt()[sid] + eps)
+    return Rn, valid
+
+
+def a2c_losses(policy: Policy, obs: torch.Tensor, actions: torch.Tensor, rewards: torch.Tensor,
+               dones: torch.Tensor, gamma: float = 0.99, eps: Optional[float] = None, targets=None):
+    """Batched ``finish_episode`` (examples/ball_cnn_ac3.py:222-246) over a recorded rollout.
+
+    obs (T, N, F) u8 -- the obs each action was chosen from; actions (T, N); rewards (T, N)
+    f64; dones (T, N) bool.  Every maximal run of an env's steps that ends at a done (or at
+    the horizon) is one episode, as ``policy.rewards`` / ``policy.saved_actions`` are in the
+    reference.  Per episode, exactly as there:
+      R_t = r_t + gamma R_{t+1} (python floats), then torch.tensor(R) (fp32),
+      R^ = (R - R.mean()) / (R.std() + eps)          (unbiased std, eps = fp32 eps),
+      policy loss  sum_t -log pi(a_t|s_t) * (R^_t - v_t.item()),
+      value loss   sum_t smooth_l1(v_t, R^_t).
+    Episodes of one step are skipped (the driver only trains when t > 0, :614).
+    log pi and v are recomputed from ``obs`` with autograd (the rollout's own values are
+    the same forward, taken without a graph).  Returns (policy_loss, value_loss) sums.
+
+    targets: ``(returns_norm, valid)``, both (T, N) -- R^ and the "episode has >= 2 steps" mask
+    computed elsewhere (``a2c_targets`` / ``Rollout.targets``: one HIP kernel); the return
+    recursion and the per-episode statistics below are then skipped, the rest is the same.
+    """
+    T, N = rewards.shape
+    if targets is None:
+        Rn, valid = _torch_targets(rewards, dones, gamma, eps)
+    else:
+        Rn, valid = targets[0], targets[1]
+        if tuple(Rn.shape) != (T, N) or tuple(valid.shape) != (T, N):
+            raise ValueError("targets must be (returns_norm, valid), both (T, N)")
+        Rn, valid = Rn.reshape(-1), valid.reshape(-1).to(torch.bool)
     probs, v = policy(obs.reshape(T * N, -1).float())
     v = v.squeeze(-1)
     logp = torch.log(probs.gather(-1, actions.reshape(-1, 1).long()).squeeze(-1))
@@ -227,12 +302,20 @@ def a2c_losses(policy: Policy, obs: torch.Tensor, actions: torch.Tensor, rewards
     return pl, vl
 
 
-def a2c_update(rollout: "Rollout", optimizer, gamma: float = 0.99):
+def a2c_update(rollout: "Rollout", optimizer, gamma: float = 0.99, targets: str = "torch"):
     """One A2C step on a recorded rollout (record_obs=True): loss.backward(), optimizer.step(),
-    then re-pack the new weights for the HIP policy kernel.  Returns the loss value."""
+    then re-pack the new weights for the HIP policy kernel.  Returns the loss value.
+    targets: "torch" (a2c_losses' own recursion and statistics) or "hip" (``Rollout.targets``)."""
     if rollout.obs is None:
         raise ValueError("a2c_update needs Rollout(record_obs=True)")
-    pl, vl = a2c_losses(rollout.policy, rollout.obs[:-1], rollout.actions, rollout.rewards, rollout.dones, gamma)
+    if targets not in ("torch", "hip"):
+        raise ValueError("targets must be 'torch' or 'hip'")
+    tg = None
+    if targets == "hip":
+        t = rollout.targets(gamma, with_returns=False)
+        tg = (t.returns_norm, t.valid)
+    pl, vl = a2c_losses(rollout.policy, rollout.obs[:-1], rollout.actions, rollout.rewards, rollout.dones, gamma,
+                        targets=tg)
     loss = pl + vl
     optimizer.zero_grad()
     loss.backward()

@@ -319,6 +319,35 @@ int64_t be_policy_bytes(const be_policy* pol);
  * in its 20-px block of the 5x5 grid -- as u8 (out) and/or f32 (out_f32; NULL = skip). */
 int be_observe_blocks(be_ctx* ctx, const be_state* st, uint8_t* out, float* out_f32, void* stream);
 
+/* ---- A2C targets: the batched finish_episode (examples/ball_cnn_ac3.py:222-246) ----
+ * From a recorded rollout of `steps` rows of ctx's N envs -- contiguous (steps, N) device
+ * arrays: rewards f64, dones u8 0/1 (what be_out.done and the rollouts write), values f32 or
+ * NULL; bootstrap (N) f64 or NULL: the return carried into the last, horizon-cut run -- the
+ * per-episode normalised returns the policy and value losses are built from.  An episode of
+ * env n is a maximal run of steps s..e with done[e] set or e = steps-1, and s = 0 or
+ * done[s-1] set.  The arithmetic is pinned, so the outputs are reproducible bit for bit:
+ *   1. walking t = steps-1 .. 0: acc = bootstrap[n] (or 0) at first, acc = 0 whenever done[t]
+ *      is set, then acc = rewards[t] + gamma * acc (one f64 multiply, one f64 add, no FMA);
+ *      R[t] = acc
+ *   2. r32[t] = (float)R[t]
+ *   3. mean = (sum of r32 in f64, accumulated in decreasing t) / L        (L = e - s + 1)
+ *   4. ss = sum of (r32 - mean)^2 in f64, accumulated in increasing t
+ *   5. L >= 2: std = sqrt(ss / (L-1)), returns_norm[t] = (float)(((double)r32[t] - mean) /
+ *      (std + eps)), valid = 1, advantage[t] = returns_norm[t] - values[t] in f32
+ *   6. L == 1 (never trained on, :614): returns_norm = 0, advantage = 0, valid = 0 (written).
+ * Asynchronous on `stream`, no allocation and no synchronisation (graph-capturable).  While
+ * the kernel runs returns_norm and valid hold intermediate values.                        */
+typedef struct be_a2c_out {
+  double*  returns;       /* (T, N) f64 R_t, or NULL                                   */
+  float*   returns_norm;  /* (T, N) f32 normalised return, required                    */
+  float*   advantage;     /* (T, N) f32 returns_norm - values, or NULL (needs values)  */
+  uint8_t* valid;         /* (T, N) 1: the element's episode has >= 2 steps; required  */
+} be_a2c_out;
+
+int be_a2c_targets(be_ctx* ctx, const double* rewards, const uint8_t* dones, const float* values,
+                   const double* bootstrap, int32_t steps, double gamma, double eps,
+                   const be_a2c_out* out, void* stream);
+
 /* ---- the createBoard physics profile ----
  * N independent ballenv_pygame.createBoard worlds (reset :460-513, step :650-675,
  * calc_reward :680-706) with the 20 featureExtractor features (featureExtractor.py:247-265)
