@@ -170,7 +170,8 @@ template <class T>
 __device__ __forceinline__ void pool_st(uint32_t* pool, uint32_t off, T v, uint32_t imm = 0) {
   *reinterpret_cast<T*>(reinterpret_cast<char*>(pool) + (size_t)off + imm) = v;
 }
-// BE_POOL_MODE (A/B): where a step kernel loads the pool entries of its finished envs.
+// BE_POOL_MODE (A/B): where stepw_kernel loads the pool entries of its finished envs (step2_kernel
+// loads them at the head of its finishing path, which only the waves with a finished env run).
 //   1: right after done is known, before the physics stores, waited for inside that (divergent)
 //      branch -- only the waves with a finished env wait;
 //   5: inside the reset section (the uniform `if (m)` of the waves with a finished env), after the
@@ -211,6 +212,19 @@ __device__ __forceinline__ T ld_s(const T* base, uint32_t idx) {
 }
 // Output / state stores of the fixed-shape step kernels: write-through (sc1, a relaxed agent-scope
 // atomic store), so the stores drain while the wave runs instead of in the kernel-end L2 write-back.
+// step2_kernel's finishing path (A/B; us per launch at 65 536 / 32 768 envs, the parent 5.66-5.69 /
+// 4.59-4.60: profiles/r07_step2_finish_path_ab.txt)
+//   BE_S2_FIN_LOAD   1: every lane loads its own env's pool entry, no branch, not waited for;
+//                    0: only the finishing lanes, in their branch, waited in place (5.73-5.89 / 4.85-5.00)
+//   BE_S2_FIN_ORDER  the episode-statistics fold: 1 before the raster (5.49-5.52 / 4.68-4.69),
+//                    2 between the raster and the entry wait (5.64-5.67 / 4.81-4.82),
+//                    3 after the copy-out, off the path to the wave's last obs store (5.39-5.42 / 4.51)
+#ifndef BE_S2_FIN_LOAD
+#define BE_S2_FIN_LOAD 1
+#endif
+#ifndef BE_S2_FIN_ORDER
+#define BE_S2_FIN_ORDER 3
+#endif
 #ifndef BE_S2_CT
 #define BE_S2_CT 256        // step2_kernel: threads per block (A/B)
 #endif
@@ -1836,6 +1850,10 @@ __global__ __launch_bounds__(BLOCK_THREADS) void be_kernel(KParams p) {
 //    instruction stream, so no extra issue).
 // Autoreset is wave_resets with the even lanes as owners; stats fold per wave (32 envs =
 // one be_stats_slots slot) in env order, as be_kernel's half-wave folds do.
+// After `done` is known the kernel exists twice: a wave with no finished env runs the lean path
+// (stores, raster, stage, copy-out), a wave with one the finishing path (pool entry loads, stores,
+// one raster for the obs and the terminal obs, the resets, the obs, the statistics fold); the two
+// never re-merge (the split below).
 // byte sel of x times k (24-bit), as one SDWA multiply: the compiler folds a byte select back into a
 // shift and a mask, which costs two more VALU per obs word
 __device__ __forceinline__ uint32_t mul24_byte(uint32_t x, uint32_t k, int sel) {
@@ -1874,6 +1892,14 @@ __global__ __launch_bounds__(S2_CT, 2) void step2_kernel(KParams p) {
   uint8_t* stage_blk = smem + (size_t)(SS + SD + 1) * CT * 4;   // [EPB envs][F]
   const bool valid = i < N;
   const uint32_t ic = (uint32_t)min(i, N - 1), gid = (uint32_t)p.gid0 + (uint32_t)i;
+  // the output / state pointers that both paths after the split store through, read here, in the
+  // entry block: read where they are used, each path began with its own chain of scalar loads
+  // (one round trip after another in front of the physics stores)
+  const struct {
+    double *reward, *ep_return, *prev_dist; int32_t *agent, *ep_len, *dyn_obs;
+    uint8_t *dyn_goal, *done, *truncated, *obs; float* obs_f32; int* status; const uint32_t* pool;
+  } ptr = {p.reward, p.ep_return, p.prev_dist, p.agent, p.ep_len, p.dyn_obs,
+         p.dyn_goal, p.done, p.truncated, p.obs, p.obs_f32, p.status, p.pool};
   NearList<CT> nl{reinterpret_cast<uint32_t*>(smem) + tid, 0};
   Tables& t = t_wave[w].t;
   const uint64_t* span = t_wave[w].span;
@@ -1913,8 +1939,8 @@ __global__ __launch_bounds__(S2_CT, 2) void step2_kernel(KParams p) {
   // caches (a pre-sampled action tape) delays only the work that needs it (6.46 -> 6.37 us with
   // cache-resident rows, 6.92 -> 6.79 us with rows from HBM)
   const int a = ld_s(p.actions, ic);
-  // the wave's stats slot (one per 32 envs), read now: a wave with a finished env updates it at
-  // the very end, and a dependent load there would lengthen exactly the waves that reset
+  // the wave's stats slot (one per 32 envs), read now: a wave with a finished env updates it at the
+  // end of its finishing path, and a dependent load there would lengthen exactly the waves that reset
   double* const slot = p.stats ? p.stats + (size_t)(e0 / 32) * 8 : nullptr;
   double2 sp0 = make_double2(0.0, 0.0), sp1 = sp0, sp2 = sp0;
   if (slot && lane == 0 && e0 < N) {
@@ -2013,170 +2039,17 @@ __global__ __launch_bounds__(S2_CT, 2) void step2_kernel(KParams p) {
   const bool trunc = p.time_limit > 0 && len >= p.time_limit;
   const bool done = env_done || trunc;
   const bool do_reset = valid && done && p.autoreset;
-  // ---- a finished env's next episode from the autoreset pool: its tag and its 112-byte body (both
-  //      lanes, the same addresses) are loaded here and land while the wave stores the physics
-  // (POOL instances are launched only with KParams::pool set; testing the pointer as well measured
-  // faster -- the compiler schedules the kernel around the branch differently: 5.65-5.71 against
-  // 5.81-5.85 us at 65 536 envs, 4.58-4.59 against 4.78-4.79 at 32 768, profiles/r06_pool_ab.txt)
-  const bool ptry = POOL && do_reset && p.pool != nullptr;
-  uint2 q_tv = make_uint2(0u, 0u);
-  uint4 qb[7];
-#if BE_POOL_MODE == 1 || BE_POOL_MODE == 6
-  if constexpr (POOL)
-#if BE_POOL_MODE == 6   // (A/B) a uniform scalar branch around the divergent one
-  if (__ballot(ptry))
-#endif
-  if (ptry) {
-    const uint32_t x = ((episode + 1u) & 1u) * (uint32_t)N + (uint32_t)i;
-    q_tv = pool_ld<uint2>(p.pool, x * 8u);
-    const uint32_t bo = pool_body((uint32_t)N, x, 28);
-#pragma unroll
-    for (int j = 0; j < 7; ++j) qb[j] = pool_ld<uint4>(p.pool, bo, 16u * j);
-    __builtin_amdgcn_s_waitcnt(0);   // here, in the branch: no pending pool load past its end
-  }
-#ifdef BE_DIAG_STAMPS
-  if (__ballot(ptry)) DIAG(9);   // (stamps build: this wave's entries landed)
-#endif
-#endif
-  if (valid) {   // both lanes of the pair store the env's scalars (the same value to the same address:
-                 // one full-wave store per array, no per-lane pointer selects or exec masking)
-    const uint32_t iu = (uint32_t)i;
-    st_ws(p.reward, iu, reward);
-    st_ws(p.ep_return, iu, ret);
-    st_ws(p.agent, iu, pk(ax, ay));
-    st_ws(p.ep_len, iu, len);
-    if (p.done) st_ws(p.done, iu, (uint8_t)done);
-    if (p.truncated) st_ws(p.truncated, iu, (uint8_t)(trunc && !env_done));
-    st_ws(p.prev_dist, iu, dist);
-    if (done) {
-      if (p.final_return) st_ws(p.final_return, iu, ret);
-      if (p.final_len) st_ws(p.final_len, iu, len);
-    }
-    // (stored after done is known: measured faster than storing inside the obstacle loop)
-#pragma unroll
-    for (int j = 0; j < SD; ++j) {
-      const int k = L * j + h;
-      if (k < NDC) {
-        st_wt(&ld_s_ptr(p.dyn_obs, (uint32_t)k * (uint32_t)N + (uint32_t)i), dnew[j]);
-        if (change) st_wt(&ld_s_ptr(p.dyn_goal, (uint32_t)k * (uint32_t)N + (uint32_t)i), (uint8_t)ngs[j]);
-      }
-    }
-  }
-  DIAG(2);
-  if (__ballot(st_flags != 0u)) {   // rare: OR the wave's flags, one atomic
-    uint32_t f = st_flags;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) f |= (uint32_t)__shfl_xor((int)f, o);
-    if (lane == 0) atomicOr(p.status, (int)f);
-  }
-  if (DBG(DBG_EXIT_PHYSICS)) return;
-
-  // ---- episode boundary: terminal obs, then the reset of the finished envs
-  uint32_t xrows[KR];
-#pragma unroll
-  for (int k = 0; k < KR; ++k) xrows[k] = 0u;
-  if (do_reset && p.terminal_obs) {   // both lanes of the pair take this branch together
-    uint32_t rows[KR], flat[NW];
-    raster_rows_span<WT, CT>(nl, p.R, rows, span);
-#pragma unroll
-    for (int k = 0; k < KR; ++k) rows[k] = pair_or(rows[k]);
-    flatten<WT>(rows, flat);
-    if (!h) write_row_global<WT>(p.terminal_obs + (int64_t)i * F, flat, quadrant(ax, ay, gx, gy));
-  }
-  // a pool entry for the new episode (e + 1) that was written and is still current: copy it.  Only
-  // the waves with a finished env take this (uniform) branch, so no other wave waits for the loads
-  // above -- every use of a loaded value is inside it
-  bool hit = false;
-#if BE_POOL_MODE == 5
-  const unsigned long long m0 = DBG(DBG_NO_RESET) ? 0ull : __ballot(do_reset && h == 0);
-  if (m0) {   // (uniform) the waves with a finished env
-  if (POOL) {
-    if (ptry) {
-      const uint32_t x = ((episode + 1u) & 1u) * (uint32_t)N + (uint32_t)i;
-      q_tv = pool_ld<uint2>(p.pool, x * 8u);
-      const uint32_t bo = pool_body((uint32_t)N, x, 28);
-#pragma unroll
-      for (int j = 0; j < 7; ++j) qb[j] = pool_ld<uint4>(p.pool, bo, 16u * j);
-    }
-#else
-  if (__ballot(ptry)) {
-#endif
-    hit = ptry && q_tv.x == episode + 1u && (q_tv.y & POOL_VALID) != 0u;
-    if (hit) {   // both lanes store the env's scalars (as the physics did) and their own obstacle slots
-      auto qw = [&](int k) -> uint32_t { return u4w(qb[k >> 2], k & 3); };   // body word k (compile-time k)
-      const uint32_t iu = (uint32_t)i;
-      const int32_t ag = (int32_t)qw(PB_AGENT), go = (int32_t)qw(PB_GOAL);
-      st_ws(p.ep_return, iu, 0.0);
-      st_ws(p.ep_len, iu, 0);
-      st_ws(p.agent, iu, ag);
-      st_ws(p.prev_dist, iu, u2d(qw(PB_PREV), qw(PB_PREV + 1)));
-      st_ws(p.goal, iu, go);
-      st_ws(p.total_dist, iu, u2d(qw(PB_TOTAL), qw(PB_TOTAL + 1)));
-      st_ws(p.episode, iu, episode + 1u);
-#pragma unroll
-      for (int j = 0; j < SD; ++j) {
-        const int k = L * j + h;
-        const uint32_t o = h ? qw(PB_OBS + NSC + min(L * j + 1, NDC - 1)) : qw(PB_OBS + NSC + L * j);
-        if (k < NDC) {
-          st_ws(p.dyn_obs, (uint32_t)k * (uint32_t)N + iu, (int32_t)o);
-          st_ws(p.dyn_goal, (uint32_t)k * (uint32_t)N + iu, (uint8_t)k);
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < SS; ++j) {
-        const int k = L * j + h;
-        const uint32_t o = h ? qw(PB_OBS + min(L * j + 1, NSC - 1)) : qw(PB_OBS + L * j);
-        if (k < NSC) st_ws(p.static_obs, (uint32_t)k * (uint32_t)N + iu, (int32_t)o);
-      }
-      ax = px(ag); ay = py(ag); gx = px(go); gy = py(go);
-#pragma unroll
-      for (int k = 0; k < KR; ++k) xrows[k] = (qw(PB_ROWS + k / 3) >> (10 * (k % 3))) & 0x3FFu;   // three rows per word
-      nl.cnt = 0;
-    }
-    if (__ballot(hit && (q_tv.y & POOL_REJ)) && lane == 0) atomicOr(p.status, BE_STATUS_REJECTION_LIMIT);
-  }
-  const unsigned long long m = DBG(DBG_NO_RESET) ? 0ull : __ballot(do_reset && !hit && h == 0);
-  if (m) {   // stale entries (or no pool): wave-cooperative, this wave runs its own resets
-    auto osink = [&](int, int k, int il, int32_t o) {   // (32-bit element offsets: pick_kernel keeps NS*N < 2^30)
-      if (k < NSC) {
-        st_ws(p.static_obs, (uint32_t)k * (uint32_t)N + (uint32_t)il, o);
-      } else {
-        st_ws(p.dyn_obs, (uint32_t)(k - NSC) * (uint32_t)N + (uint32_t)il, o);
-        st_ws(p.dyn_goal, (uint32_t)(k - NSC) * (uint32_t)N + (uint32_t)il, (uint8_t)(k - NSC));
-      }
-    };
-    auto esink = [&](int, int32_t ag, int32_t go, int32_t a0) {
-      // both lanes take the new agent / goal / rows and store the env's scalars, as in the physics
-      // above.  Ordering against the physics stores is the wave's program order (wave_resets' note)
-      double prev;
-      const double td = reset_dists(ag, go, a0, prev);
-      const uint32_t iu = (uint32_t)i;
-      st_ws(p.ep_return, iu, 0.0);
-      st_ws(p.ep_len, iu, 0);
-      st_ws(p.agent, iu, ag);
-      st_ws(p.prev_dist, iu, prev);
-      st_ws(p.goal, iu, go);
-      st_ws(p.total_dist, iu, td);
-      st_ws(p.episode, iu, episode + 1u);
-    };
-    if (!(m & (m - 1)))
-      wave_resets<WT, NSC, NDC, 1, decltype(osink)&, decltype(esink)&, L>(p, t, m, i, gid, episode, ax, ay, gx, gy,
-                                                                        nl.cnt, xrows, &s_rows[w][0], osink, esink, span);
-    else
-      wave_resets<WT, NSC, NDC, 64, decltype(osink)&, decltype(esink)&, L>(p, t, m, i, gid, episode, ax, ay, gx, gy,
-                                                                         nl.cnt, xrows, &s_rows[w][0], osink, esink, span);
-  }
-#if BE_POOL_MODE == 5
-  }
-#endif
-  DIAG(3);
-  if (DBG(DBG_NO_OBS)) return;
-  if (DBG(DBG_NO_RASTER)) nl.cnt = 0;
-
-  // ---- observation (prep_state4): own near list -> rows, OR-ed over the pair, half a row each
-  {
-    uint32_t rows[KR];
-    raster_rows_span<WT, CT>(nl, p.R, rows, span, xrows);   // from a reset env's new rows (else 0)
+  // ---- the wave-uniform split.  From here the kernel exists twice, as the two instantiations of
+  //      one inlined body, and the two never re-merge: ~99 % of the waves hold no finished env and
+  //      run the lean path (FIN = false: physics stores, raster from zero rows, stage, copy-out --
+  //      no pool code, no terminal obs, no reset ballots, no statistics fold); a wave with a
+  //      finished env runs the finishing path (FIN = true), ordered so that its pool entries'
+  //      round trip is covered by the stores, the statistics fold and the raster.
+  //      The ballot is on done, not do_reset: with autoreset off the wave still has final_* to store
+  //      and statistics to fold.
+  // the observation (prep_state4) from the env's distinct rows: OR-ed over the pair, half a row each
+  // into the wave's stage, then the wave's contiguous rows out
+  auto obs_out = [&](const uint32_t (&rows)[KR]) __attribute__((always_inline)) {
     // three 10-bit rows per word, OR-ed over the pair (3 DPP ops); then this lane's cells from its
     // first nibble: lane 0 cells -4.. (its word 0 is the quadrant one-hot), lane 1 cells 52..  Window
     // row r is distinct row max(r-1, 0) (quirk Q1): V = sum_r R_r << (10 r + 4) over the lane's six
@@ -2206,30 +2079,225 @@ __global__ __launch_bounds__(S2_CT, 2) void step2_kernel(KParams p) {
       const uint32_t w0 = q == 0 ? (h ? word(0) : onehot) : word(2 * q);
       if (q < NQ - HQ || !h) dst[q] = make_uint2(w0, word(2 * q + 1));
     }
-  }
-  DIAG(4);
-  // the wave's contiguous rows out (no block barrier: a wave that reset delays nobody)
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  DIAG(5);
-  if (!DBG(DBG_NO_COPY)) {
-    const int e0u = __builtin_amdgcn_readfirstlane(e0);
-    if (e0u + EPW <= N && p.obs && !p.obs_f32)   // the common case: a full wave, u8 obs only
-      copy_wave_full<EPW * F / 16>(stage, p.obs + (size_t)e0u * F, lane);
-    else
-      copy_out<64>(stage, F, max(0, min(EPW, N - e0u)), (int64_t)e0u, p.obs, p.obs_f32, lane);
-  }
-  // the episode statistics fold after the obs stores are issued: off the path to the last store
-  // (6.55 -> 6.45 us; a reset leaves this lane's ret / len registers as the finished episode's)
-  WaveStats ws{0.0, 0.0, 0.0, 0.0, INFINITY, -INFINITY};
-  if (slot && !DBG(DBG_NO_STATS)) ws = wave_stats(done && valid && h == 0, ret, len);   // even lanes: env order
-  if (slot && lane == 0 && ws.n > 0.0) {
-    reinterpret_cast<double2*>(slot)[0] = make_double2(sp0.x + ws.n, sp0.y + ws.s1);
-    reinterpret_cast<double2*>(slot)[1] = make_double2(sp1.x + ws.s2, sp1.y + ws.sl);
-    reinterpret_cast<double2*>(slot)[2] = make_double2(fmin(sp2.x, ws.mn), fmax(sp2.y, ws.mx));
-  }
-  DIAG(6);
+    DIAG(4);
+    // the wave's contiguous rows out (no block barrier: a wave that reset delays nobody)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    DIAG(5);
+    if (!DBG(DBG_NO_COPY)) {
+      const int e0u = __builtin_amdgcn_readfirstlane(e0);
+      if (e0u + EPW <= N && ptr.obs && !ptr.obs_f32)   // the common case: a full wave, u8 obs only
+        copy_wave_full<EPW * F / 16>(stage, ptr.obs + (size_t)e0u * F, lane);
+      else
+        copy_out<64>(stage, F, max(0, min(EPW, N - e0u)), (int64_t)e0u, ptr.obs, ptr.obs_f32, lane);
+    }
+  };
+  auto tail = [&](auto fin_c) __attribute__((always_inline)) {
+    constexpr bool FIN = decltype(fin_c)::value;
+    // (FIN) every lane of the wave loads the pool entry of its own env's next episode: the tag and
+    // the 112-byte body, both lanes of a pair the same addresses, the lanes past N the last env's.
+    // Straight-line and not waited for here -- no branch surrounds the loads, so the compiler counts
+    // vmcnt down to them at their first use, after the stores and the raster below.  Only
+    // the ~15 waves of a launch with a finished env read these ~4 KB.  (POOL instances are launched
+    // only with KParams::pool set: be_step picks them by it.)
+    uint2 q_tv = make_uint2(0u, 0u);
+    uint4 qb[7];
+    if constexpr (FIN && POOL) {
+#if BE_S2_FIN_LOAD == 1
+      const uint32_t x = ((episode + 1u) & 1u) * (uint32_t)N + ic;
+      q_tv = pool_ld<uint2>(ptr.pool, x * 8u);
+      const uint32_t bo = pool_body((uint32_t)N, x, 28);
+#pragma unroll
+      for (int j = 0; j < 7; ++j) qb[j] = pool_ld<uint4>(ptr.pool, bo, 16u * j);
+#else
+      if (do_reset) {   // only the finishing lanes load, and wait here: no pending load past the branch
+        const uint32_t x = ((episode + 1u) & 1u) * (uint32_t)N + (uint32_t)i;
+        q_tv = pool_ld<uint2>(ptr.pool, x * 8u);
+        const uint32_t bo = pool_body((uint32_t)N, x, 28);
+#pragma unroll
+        for (int j = 0; j < 7; ++j) qb[j] = pool_ld<uint4>(ptr.pool, bo, 16u * j);
+        __builtin_amdgcn_s_waitcnt(0);
+      }
+#endif
+    }
+    if (valid) {   // both lanes of the pair store the env's scalars (the same value to the same address:
+                   // one full-wave store per array, no per-lane pointer selects or exec masking)
+      const uint32_t iu = (uint32_t)i;
+      st_ws(ptr.reward, iu, reward);
+      st_ws(ptr.ep_return, iu, ret);
+      st_ws(ptr.agent, iu, pk(ax, ay));
+      st_ws(ptr.ep_len, iu, len);
+      // (the lean path: no valid lane of the wave is done)
+      if (ptr.done) st_ws(ptr.done, iu, (uint8_t)(FIN && done));
+      if (ptr.truncated) st_ws(ptr.truncated, iu, (uint8_t)(FIN && trunc && !env_done));
+      st_ws(ptr.prev_dist, iu, dist);
+      if constexpr (FIN) {
+        if (done) {
+          if (p.final_return) st_ws(p.final_return, iu, ret);
+          if (p.final_len) st_ws(p.final_len, iu, len);
+        }
+      }
+      // (stored after done is known: measured faster than storing inside the obstacle loop)
+#pragma unroll
+      for (int j = 0; j < SD; ++j) {
+        const int k = L * j + h;
+        if (k < NDC) {
+          st_wt(&ld_s_ptr(ptr.dyn_obs, (uint32_t)k * (uint32_t)N + (uint32_t)i), dnew[j]);
+          if (change) st_wt(&ld_s_ptr(ptr.dyn_goal, (uint32_t)k * (uint32_t)N + (uint32_t)i), (uint8_t)ngs[j]);
+        }
+      }
+    }
+    DIAG(2);
+    if (__ballot(st_flags != 0u)) {   // rare: OR the wave's flags, one atomic
+      uint32_t f = st_flags;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) f |= (uint32_t)__shfl_xor((int)f, o);
+      if (lane == 0) atomicOr(ptr.status, (int)f);
+    }
+    if (DBG(DBG_EXIT_PHYSICS)) return;
+
+    if constexpr (!FIN) {   // ---- the lean path: the obs from this lane's own near list
+      DIAG(3);
+      if (DBG(DBG_NO_OBS)) return;
+      if (DBG(DBG_NO_RASTER)) nl.cnt = 0;
+      uint32_t rows[KR];
+      raster_rows_span<WT, CT>(nl, p.R, rows, span);
+      obs_out(rows);
+      DIAG(6);
+      return;
+    } else {
+      // ---- the finishing path.  The episode statistics fold needs only done, ret and len (even
+      // lanes: env order; a reset leaves them alone), so it can run anywhere: after the obs stores
+      // are issued measured fastest (BE_S2_FIN_ORDER) -- the ballot loop's readlanes and the f64
+      // adds are then behind the wave's last obs store instead of in front of the entry wait
+      auto fold = [&]() __attribute__((always_inline)) {
+        if (slot && !DBG(DBG_NO_STATS)) {
+          const WaveStats ws = wave_stats(done && valid && h == 0, ret, len);
+          if (lane == 0 && ws.n > 0.0) {
+            reinterpret_cast<double2*>(slot)[0] = make_double2(sp0.x + ws.n, sp0.y + ws.s1);
+            reinterpret_cast<double2*>(slot)[1] = make_double2(sp1.x + ws.s2, sp1.y + ws.sl);
+            reinterpret_cast<double2*>(slot)[2] = make_double2(fmin(sp2.x, ws.mn), fmax(sp2.y, ws.mx));
+          }
+        }
+      };
+#if BE_S2_FIN_ORDER == 1
+      fold();
+#endif
+      // ONE raster of every lane's own near list: the obs rows of the lanes that do not reset, and,
+      // OR-ed over the pair and flattened, the terminal obs of the ones that do (its byte stores wait
+      // until the entries have landed)
+      if (DBG(DBG_NO_RASTER)) nl.cnt = 0;
+      uint32_t xrows[KR];
+      raster_rows_span<WT, CT>(nl, p.R, xrows, span);
+      const bool tobs = do_reset && p.terminal_obs != nullptr;
+      uint32_t tflat[NW];
+      const int tquad = quadrant(ax, ay, gx, gy);
+      if (p.terminal_obs) {   // (uniform)
+        uint32_t rows[KR];
+#pragma unroll
+        for (int k = 0; k < KR; ++k) rows[k] = pair_or(xrows[k]);
+        flatten<WT>(rows, tflat);
+      }
+#if BE_S2_FIN_ORDER == 2
+      fold();
+#endif
+      // ---- episode boundary.  A pool entry for the new episode (e + 1) that was written and is still
+      // current: copy it (the first use of the loaded values: the wave waits for its entries here)
+      bool hit = false;
+      if constexpr (POOL) {
+        // every loaded word is consumed here, on every path (also the entry's padding, and in a wave
+        // whose finished envs do not reset): with a load left pending to the end of this path the
+        // waitcnt pass put its wait into the lean path as well (a vmcnt(0) in the raster loop and a
+        // counted one in front of the obs stores, which there wait for the physics stores).  Empty
+        // asm statements: they emit no instruction and only make the values used here; a plain C++
+        // use that the results do not need is removed by the optimiser.  The cost is that a
+        // finishing wave with no resetting env (autoreset off) waits for its entries as well
+#if BE_S2_FIN_LOAD == 1
+        asm volatile("" :: "v"(q_tv.x), "v"(q_tv.y));
+#pragma unroll
+        for (int j = 0; j < 7; ++j) asm volatile("" :: "v"(qb[j].x), "v"(qb[j].y), "v"(qb[j].z), "v"(qb[j].w));
+#endif
+        hit = do_reset && q_tv.x == episode + 1u && (q_tv.y & POOL_VALID) != 0u;
+#ifdef BE_DIAG_STAMPS
+        if (__ballot(do_reset)) DIAG(9);   // (stamps build: this wave's entries landed)
+#endif
+        if (hit) {   // both lanes store the env's scalars (as the physics did) and their own obstacle slots
+          auto qw = [&](int k) -> uint32_t { return u4w(qb[k >> 2], k & 3); };   // body word k (compile-time k)
+          const uint32_t iu = (uint32_t)i;
+          const int32_t ag = (int32_t)qw(PB_AGENT), go = (int32_t)qw(PB_GOAL);
+          st_ws(ptr.ep_return, iu, 0.0);
+          st_ws(ptr.ep_len, iu, 0);
+          st_ws(ptr.agent, iu, ag);
+          st_ws(ptr.prev_dist, iu, u2d(qw(PB_PREV), qw(PB_PREV + 1)));
+          st_ws(p.goal, iu, go);
+          st_ws(p.total_dist, iu, u2d(qw(PB_TOTAL), qw(PB_TOTAL + 1)));
+          st_ws(p.episode, iu, episode + 1u);
+#pragma unroll
+          for (int j = 0; j < SD; ++j) {
+            const int k = L * j + h;
+            const uint32_t o = h ? qw(PB_OBS + NSC + min(L * j + 1, NDC - 1)) : qw(PB_OBS + NSC + L * j);
+            if (k < NDC) {
+              st_ws(ptr.dyn_obs, (uint32_t)k * (uint32_t)N + iu, (int32_t)o);
+              st_ws(ptr.dyn_goal, (uint32_t)k * (uint32_t)N + iu, (uint8_t)k);
+            }
+          }
+#pragma unroll
+          for (int j = 0; j < SS; ++j) {
+            const int k = L * j + h;
+            const uint32_t o = h ? qw(PB_OBS + min(L * j + 1, NSC - 1)) : qw(PB_OBS + L * j);
+            if (k < NSC) st_ws(p.static_obs, (uint32_t)k * (uint32_t)N + iu, (int32_t)o);
+          }
+          ax = px(ag); ay = py(ag); gx = px(go); gy = py(go);
+#pragma unroll
+          for (int k = 0; k < KR; ++k) xrows[k] = (qw(PB_ROWS + k / 3) >> (10 * (k % 3))) & 0x3FFu;   // three rows per word
+        }
+        if (__ballot(hit && (q_tv.y & POOL_REJ)) && lane == 0) atomicOr(ptr.status, BE_STATUS_REJECTION_LIMIT);
+      }
+      // the terminal obs of the envs that reset, from the shared raster (before their new agent / goal)
+      if (tobs && !h) write_row_global<WT>(p.terminal_obs + (int64_t)i * F, tflat, tquad);
+      const unsigned long long m = DBG(DBG_NO_RESET) ? 0ull : __ballot(do_reset && !hit && h == 0);
+      if (m) {   // stale entries (or no pool): wave-cooperative, this wave runs its own resets
+        auto osink = [&](int, int k, int il, int32_t o) {   // (32-bit element offsets: pick_kernel keeps NS*N < 2^30)
+          if (k < NSC) {
+            st_ws(p.static_obs, (uint32_t)k * (uint32_t)N + (uint32_t)il, o);
+          } else {
+            st_ws(ptr.dyn_obs, (uint32_t)(k - NSC) * (uint32_t)N + (uint32_t)il, o);
+            st_ws(ptr.dyn_goal, (uint32_t)(k - NSC) * (uint32_t)N + (uint32_t)il, (uint8_t)(k - NSC));
+          }
+        };
+        auto esink = [&](int, int32_t ag, int32_t go, int32_t a0) {
+          // both lanes take the new agent / goal / rows and store the env's scalars, as in the physics
+          // above.  Ordering against the physics stores is the wave's program order (wave_resets' note)
+          double prev;
+          const double td = reset_dists(ag, go, a0, prev);
+          const uint32_t iu = (uint32_t)i;
+          st_ws(ptr.ep_return, iu, 0.0);
+          st_ws(ptr.ep_len, iu, 0);
+          st_ws(ptr.agent, iu, ag);
+          st_ws(ptr.prev_dist, iu, prev);
+          st_ws(p.goal, iu, go);
+          st_ws(p.total_dist, iu, td);
+          st_ws(p.episode, iu, episode + 1u);
+        };
+        if (!(m & (m - 1)))
+          wave_resets<WT, NSC, NDC, 1, decltype(osink)&, decltype(esink)&, L>(p, t, m, i, gid, episode, ax, ay, gx, gy,
+                                                                            nl.cnt, xrows, &s_rows[w][0], osink, esink, span);
+        else
+          wave_resets<WT, NSC, NDC, 64, decltype(osink)&, decltype(esink)&, L>(p, t, m, i, gid, episode, ax, ay, gx, gy,
+                                                                             nl.cnt, xrows, &s_rows[w][0], osink, esink, span);
+      }
+      DIAG(3);
+      if (DBG(DBG_NO_OBS)) return;
+      obs_out(xrows);   // a reset env's new rows, the other lanes' rows of the raster above
+#if BE_S2_FIN_ORDER == 3
+      fold();
+#endif
+      DIAG(6);
+    }
+  };
+  if (__ballot(valid && done)) tail(std::true_type{});
+  else tail(std::false_type{});
 }
 
 // ------------------------------------------------------------------ small batches at W = 5
