@@ -30,7 +30,11 @@ BASE_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math
 # tiles' accumulators in AGPRs, which costs 12 v_accvgpr_read per tile row (of ~70 VALU); only
 # the kernels with MFMAs (the policy forward and the fused policy rollouts) change.
 VGPR_MFMA = ["-mllvm", "-amdgpu-mfma-vgpr-form"]
-UNITS = {"ballenv.hip": VGPR_MFMA, "policy.hip": ["-fno-slp-vectorize", *VGPR_MFMA], "features.hip": [], "board.hip": [],
+# -amdgpu-kernarg-preload-count: leading scalar kernel arguments (up to 14 dwords) arrive in user
+# SGPRs at wave launch instead of through a scalar load from the kernarg segment (step2_kernel's
+# prologue); the compiler keeps an s_load entry for firmware without the preload.
+KARG_PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
+UNITS = {"ballenv.hip": [*VGPR_MFMA, *KARG_PRELOAD], "policy.hip": ["-fno-slp-vectorize", *VGPR_MFMA], "features.hip": [], "board.hip": [],
          "a2c.hip": []}
 HEADERS = [HDR, *(os.path.join(CSRC, h) for h in ("philox.h", "internal.h", "policy_core.h", "diag.h"))]
 

@@ -1870,8 +1870,27 @@ __device__ __forceinline__ uint32_t pair_or(uint32_t x) {   // OR with the other
   return x | (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0xB1, 0xF, 0xF, false);   // quad_perm 1,0,3,2
 }
 
+// step2_kernel's arguments (launch() fills all three from the one KParams it builds):
+//  * 14 dwords of leading scalars.  gfx950's dispatcher preloads them into user SGPRs while the
+//    wave launches (-amdgpu-kernarg-preload-count, build.py; a by-value struct is not preloaded),
+//    so the loads through them -- the tables, episode / ep_len, every obstacle -- issue at once,
+//    with no scalar load from the kernarg segment in front of them;
+//  * KHot: what the prologue's other loads go through, one 64-byte line of the kernarg segment.
+//    Its scalar load is issued first of all and is the only one the prologue waits for;
+//  * KParams, as every other kernel takes it: read after the prologue's loads are in flight.
+// (Stamps and A/B: DESIGN 3.3, profiles/r08_*.)
+struct alignas(64) KHot {
+  int32_t* agent; int32_t* goal; double* prev_dist; double* total_dist; double* ep_return;
+  const uint8_t* actions; double* stats; int32_t prev_read, goal_change;
+};
+static_assert(sizeof(KHot) == 64, "one line of the kernarg segment");
 template <int WT, int NSC, int NDC, bool POOL = false>
-__global__ __launch_bounds__(S2_CT, 2) void step2_kernel(KParams p) {
+__global__ __launch_bounds__(S2_CT, 2) void step2_kernel(const Tables* a_tables, uint32_t* a_episode, int32_t* a_ep_len,
+                                                         int32_t* a_dyn_obs, uint8_t* a_dyn_goal, int32_t* a_static_obs,
+                                                         int32_t a_n, int32_t a_gid0, KHot hot_in, KParams p) {
+  const KHot hot = {hot_in.agent, hot_in.goal, hot_in.prev_dist, hot_in.total_dist, hot_in.ep_return,
+                    hot_in.actions, hot_in.stats, hot_in.prev_read, hot_in.goal_change};
+  __builtin_amdgcn_sched_barrier(0);   // KHot's scalar load stays in front of everything below
   constexpr int CT = S2_CT;
   constexpr int L = 2, EPW = 64 / L, EPB = CT / L, NWAVE = CT / 64;
   constexpr int SS = (NSC + L - 1) / L, SD = (NDC + L - 1) / L;   // obstacle slots per lane
@@ -1887,19 +1906,12 @@ __global__ __launch_bounds__(S2_CT, 2) void step2_kernel(KParams p) {
 
   DIAG(0);
   if (DBG(DBG_EXIT_ENTRY)) return;
-  const int N = p.n, tid = (int)threadIdx.x, w = tid >> 6, lane = tid & 63, h = lane & 1;
+  const int N = a_n, tid = (int)threadIdx.x, w = tid >> 6, lane = tid & 63, h = lane & 1;
+  DIAG_SARG(0, N);
   const int blk0 = (int)blockIdx.x * EPB, i = blk0 + (tid >> 1), e0 = blk0 + w * EPW;
   uint8_t* stage_blk = smem + (size_t)(SS + SD + 1) * CT * 4;   // [EPB envs][F]
   const bool valid = i < N;
-  const uint32_t ic = (uint32_t)min(i, N - 1), gid = (uint32_t)p.gid0 + (uint32_t)i;
-  // the output / state pointers that both paths after the split store through, read here, in the
-  // entry block: read where they are used, each path began with its own chain of scalar loads
-  // (one round trip after another in front of the physics stores)
-  const struct {
-    double *reward, *ep_return, *prev_dist; int32_t *agent, *ep_len, *dyn_obs;
-    uint8_t *dyn_goal, *done, *truncated, *obs; float* obs_f32; int* status; const uint32_t* pool;
-  } ptr = {p.reward, p.ep_return, p.prev_dist, p.agent, p.ep_len, p.dyn_obs,
-         p.dyn_goal, p.done, p.truncated, p.obs, p.obs_f32, p.status, p.pool};
+  const uint32_t ic = (uint32_t)min(i, N - 1), gid = (uint32_t)a_gid0 + (uint32_t)i;
   NearList<CT> nl{reinterpret_cast<uint32_t*>(smem) + tid, 0};
   Tables& t = t_wave[w].t;
   const uint64_t* span = t_wave[w].span;
@@ -1913,41 +1925,56 @@ __global__ __launch_bounds__(S2_CT, 2) void step2_kernel(KParams p) {
   uint4 tword[TL];
 #pragma unroll
   for (int j = 0; j < TL; ++j)
-    tword[j] = ld_s(reinterpret_cast<const uint4*>(p.tables), (uint32_t)min(tt0 + j * TB, TW - 1));
-  const uint32_t episode = ld_s(p.episode, ic);
-  const int len0 = ld_s(p.ep_len, ic);
-  const int32_t agent0 = ld_s(p.agent, ic), goal0 = ld_s(p.goal, ic);
+    tword[j] = ld_s(reinterpret_cast<const uint4*>(a_tables), (uint32_t)min(tt0 + j * TB, TW - 1));
+  const uint32_t episode = ld_s(a_episode, ic);
+  const int len0 = ld_s(a_ep_len, ic);
   int32_t dp[SD], so[SS];
   int dgi[SD];
 #pragma unroll
   for (int j = 0; j < SD; ++j) {
     const uint32_t e = (uint32_t)min(L * j + h, NDC - 1) * (uint32_t)N + ic;
-    dp[j] = ld_s(p.dyn_obs, e);
-    dgi[j] = ld_s(p.dyn_goal, e);
+    dp[j] = ld_s(a_dyn_obs, e);
+    dgi[j] = ld_s(a_dyn_goal, e);
   }
 #pragma unroll
-  for (int j = 0; j < SS; ++j) so[j] = ld_s(p.static_obs, (uint32_t)min(L * j + h, NSC - 1) * (uint32_t)N + ic);
+  for (int j = 0; j < SS; ++j) so[j] = ld_s(a_static_obs, (uint32_t)min(L * j + h, NSC - 1) * (uint32_t)N + ic);
+  // (every load above goes through a preloaded argument; the ones below through KHot, the one
+  // scalar load that the prologue waits for)
+  const int32_t agent0 = ld_s(hot.agent, ic), goal0 = ld_s(hot.goal, ic);
   // state[2] of the last step (prev_read = 0: recomputed, it is calc_dist(goal, agent) -- see KParams).
   // (Read unconditionally with the select after a scheduling barrier, so that the action is issued
   // with the other loads instead of after the goal load lands: 5.26-5.27 against 5.22-5.24 us at
   // 32 768 envs, the same within noise at 65 536 -- profiles/r05_prologue_ab.txt, not kept here; it
   // is kept in the one-lane kernel, 8.05 against 8.13-8.15 us at 131 072)
-  const double old_dist = p.prev_read ? ld_s(p.prev_dist, ic) : calc_dist(px(goal0), py(goal0), px(agent0), py(agent0));
-  const double total = ld_s(p.total_dist, ic);
-  double ret = ld_s(p.ep_return, ic);
+  DIAG_SARG(1, hot.prev_read);
+  // (prev_read = 0 recomputes after the barrier: here the goal load would have to land before the
+  // loads below issue, which costs 0.2 us -- profiles/r08_kernarg_preload_ab.txt)
+  double old_dist = 0.0;
+  if (hot.prev_read) old_dist = ld_s(hot.prev_dist, ic);
+  const double total = ld_s(hot.total_dist, ic);
+  double ret = ld_s(hot.ep_return, ic);
   // the action last: the obstacle draws and moves below need no action, so a row that misses the
   // caches (a pre-sampled action tape) delays only the work that needs it (6.46 -> 6.37 us with
   // cache-resident rows, 6.92 -> 6.79 us with rows from HBM)
-  const int a = ld_s(p.actions, ic);
+  const int a = ld_s(hot.actions, ic);
   // the wave's stats slot (one per 32 envs), read now: a wave with a finished env updates it at the
   // end of its finishing path, and a dependent load there would lengthen exactly the waves that reset
-  double* const slot = p.stats ? p.stats + (size_t)(e0 / 32) * 8 : nullptr;
+  double* const slot = hot.stats ? hot.stats + (size_t)(e0 / 32) * 8 : nullptr;
   double2 sp0 = make_double2(0.0, 0.0), sp1 = sp0, sp2 = sp0;
   if (slot && lane == 0 && e0 < N) {
     sp0 = reinterpret_cast<const double2*>(slot)[0];
     sp1 = reinterpret_cast<const double2*>(slot)[1];
     sp2 = reinterpret_cast<const double2*>(slot)[2];
   }
+  // the output / state pointers that both paths after the split store through, read here, ahead
+  // of the split: read where they are used, each path began with its own chain of scalar loads
+  // (one round trip after another in front of the physics stores).  KParams is first read here,
+  // with every prologue load in flight.
+  const struct {
+    double *reward, *ep_return, *prev_dist; int32_t *agent, *ep_len, *dyn_obs;
+    uint8_t *dyn_goal, *done, *truncated, *obs; float* obs_f32; int* status; const uint32_t* pool;
+  } ptr = {p.reward, hot.ep_return, hot.prev_dist, hot.agent, a_ep_len, a_dyn_obs,
+         a_dyn_goal, p.done, p.truncated, p.obs, p.obs_f32, p.status, p.pool};
 #pragma unroll
   for (int j = 0; j < TL; ++j) reinterpret_cast<uint4*>(&t_wave[w])[min(tt0 + j * TB, TW - 1)] = tword[j];
   // this wave's copy of the tables staged (state loads retire in order as used): a wave barrier, no
@@ -1965,10 +1992,10 @@ __global__ __launch_bounds__(S2_CT, 2) void step2_kernel(KParams p) {
 
   // ---- this lane's dynamic obstacles: draws and moves first (no action needed; ballenv_env.py:323-353)
   int counter = (int)((double)len0 * p.inv_g1);   // counter == ep_len mod (G+1)
-  counter = len0 - counter * (p.goal_change + 1);
-  if (counter < 0) counter += p.goal_change + 1;
-  if (counter > p.goal_change) counter -= p.goal_change + 1;
-  const bool change = counter >= p.goal_change;
+  counter = len0 - counter * (hot.goal_change + 1);
+  if (counter < 0) counter += hot.goal_change + 1;
+  if (counter > hot.goal_change) counter -= hot.goal_change + 1;
+  const bool change = counter >= hot.goal_change;
   const u4 b0 = DBG(DBG_NO_PHILOX) ? u4{gid, episode, (uint32_t)len0, gid ^ episode}   // (ablation: wrong draws)
                                    : philox(gid, episode, (uint32_t)len0, tag(PURPOSE_STEP_OBS, 0u), p.seed);
   DIAG(7);
@@ -2001,6 +2028,13 @@ __global__ __launch_bounds__(S2_CT, 2) void step2_kernel(KParams p) {
   const v2u boxw = {(unsigned short)nb0.bw, (unsigned short)nb0.bh};
   const v2s agv = __builtin_bit_cast(v2s, pk(ax, ay));
   const double dist = calc_dist(gx, gy, ax, ay);
+  if (!hot.prev_read) {
+    // (on copies the compiler cannot see through: sharing the unpacking with the move above, it
+    // put the wait for the goal load in front of this branch, ahead of the Philox block)
+    int32_t g0 = goal0, a0 = agent0;
+    asm("" : "+v"(g0), "+v"(a0));
+    old_dist = calc_dist(px(g0), py(g0), px(a0), py(a0));
+  }
   // the distance and the distance term of the reward (ballenv_env.py:268-275) right after the
   // move: the f64 sqrt / divide chain then overlaps the obstacle tests
   const double rbase = (0.0 - p.time_penalty) + (old_dist - dist) / total;
@@ -3516,13 +3550,15 @@ __global__ void sample_actions_kernel(uint8_t* out, int32_t n, int32_t steps, in
 
 // ------------------------------------------------------------------ dispatch
 using KFn = void (*)(KParams);
+// step2_kernel: its leading scalar arguments (preloaded into SGPRs), KHot, then the KParams
+using KFn2 = void (*)(const Tables*, uint32_t*, int32_t*, int32_t*, uint8_t*, int32_t*, int32_t, int32_t, KHot, KParams);
 template <int WT>
 KFn kernel_for(int mode) {
   return mode == MODE_STEP ? be_kernel<WT, MODE_STEP>
                            : (mode == MODE_RESET ? be_kernel<WT, MODE_RESET> : be_kernel<WT, MODE_OBSERVE>);
 }
 
-struct Launch { KFn fn; int epb; int lds; char name[48]; int threads = BLOCK_THREADS; };
+struct Launch { KFn fn; int epb; int lds; char name[48]; int threads = BLOCK_THREADS; KFn2 fn2 = nullptr; };   // fn2: step2_kernel (fn is nullptr then)
 
 // Fixed-shape step kernels for the reference's default obstacle counts (ball_cnn_ac3.py:40-41).
 constexpr int FIX_NS = 13, FIX_ND = 5;   // the reference's obstacle counts (ball_cnn_ac3.py:40-41)
@@ -3544,7 +3580,7 @@ Launch pick_kernel(const be_config& c, int mode, bool fixed_ok = false, int lane
   if (fixed && lanes10 == 2 && W == 10 && span_fits(W, c.radius_obstacle + c.radius_agent) &&
       (int64_t)c.num_envs * FIX_NS < (1ll << 30)) {
     // two lanes per env (step2_kernel): 32 envs per wave, 128 per block
-    L.fn = pool ? step2_kernel<10, FIX_NS, FIX_ND, true> : step2_kernel<10, FIX_NS, FIX_ND, false>;
+    L.fn2 = pool ? step2_kernel<10, FIX_NS, FIX_ND, true> : step2_kernel<10, FIX_NS, FIX_ND, false>;
     L.epb = S2_CT / 2;
     L.threads = S2_CT;
     constexpr int SLOTS = (FIX_NS + 1) / 2 + (FIX_ND + 1) / 2 + 1;
@@ -3839,7 +3875,7 @@ const char* be_kernel_name(const be_ctx* ctx, int32_t entry) {
     case BE_ENTRY_OBSERVE: L = pick_kernel(ctx->cfg, MODE_OBSERVE, false); break;
     default: return nullptr;
   }
-  if (!L.fn) return nullptr;
+  if (!L.fn && !L.fn2) return nullptr;
   memcpy(name, L.name, sizeof name);
   return name;
 }
@@ -3972,10 +4008,11 @@ int be_create(const be_config* cfg, int32_t device, be_ctx** out) {
   ctx->step_launch[1] = pick_kernel(ctx->cfg, MODE_STEP, true, ctx->step_lanes, ctx->step5_lpe);
   {  // the autoreset pool, for the fixed-shape kernels that consume it (step2_kernel, stepw_kernel, the one-lane kernel)
     const KFn f = ctx->step_launch[1].fn;
+    const KFn2 f2 = ctx->step_launch[1].fn2;
     int64_t onelane_max = (int64_t)2 * 64 * 4 * cus;   // BALLENV_POOL_ONELANE_MAX: the bound below, for A/B runs
     if (const char* v = getenv("BALLENV_POOL_ONELANE_MAX")) onelane_max = atoll(v);
     const bool consumes = ctx->unit_moves && ctx->distinct_goals && !ctx->generic_only && cfg->autoreset &&
-                          (f == step2_kernel<10, FIX_NS, FIX_ND, false> || f == stepw_kernel<5, FIX_NS, FIX_ND, 8, false> ||
+                          (f2 == step2_kernel<10, FIX_NS, FIX_ND, false> || f == stepw_kernel<5, FIX_NS, FIX_ND, 8, false> ||
                            f == stepw_kernel<5, FIX_NS, FIX_ND, 4, false> ||
                            // the one-lane kernel up to two waves per SIMD: 7.51-7.59 against 7.76-7.85 us at
                            // 131 072 envs; at 262 144 (four waves per SIMD hide the reset draws, and the
@@ -4071,7 +4108,14 @@ static int launch(be_ctx* ctx, int mode, KParams& a, void* stream, int32_t steps
   const int N = ctx->cfg.num_envs;
   const dim3 grid((unsigned)((N + L.epb - 1) / L.epb)), block((unsigned)L.threads);
   for (int32_t s = 0; s < steps; ++s) {
-    hipLaunchKernelGGL(L.fn, grid, block, (size_t)L.lds, (hipStream_t)stream, a);
+    if (L.fn2)
+      hipLaunchKernelGGL(L.fn2, grid, block, (size_t)L.lds, (hipStream_t)stream, a.tables, a.episode, a.ep_len, a.dyn_obs,
+                         a.dyn_goal, a.static_obs, a.n, a.gid0,
+                         KHot{a.agent, a.goal, a.prev_dist, a.total_dist, a.ep_return, a.actions, a.stats, a.prev_read,
+                              a.goal_change},
+                         a);
+    else
+      hipLaunchKernelGGL(L.fn, grid, block, (size_t)L.lds, (hipStream_t)stream, a);
     a.actions += N;
     if (use_pool && ctx->pool_period > 0 && ++ctx->pool_calls >= ctx->pool_period) launch_pool_fill(ctx, a, stream);
   }

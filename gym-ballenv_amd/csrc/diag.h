@@ -47,6 +47,18 @@ __device__ __forceinline__ void diag_stamp(int point) {
   }
 }
 #define DIAG(pt) diag_stamp(pt)
+// DIAG_SARG(k, v): prologue stamp k (0: the first kernel-argument words have landed, 1: the last
+// scalar word the prologue loads through has) -- s_memtime taken once the uniform value v sits in
+// SGPRs, i.e. after the s_waitcnt that covers its scalar load (or at once if it was preloaded)
+__device__ unsigned long long g_diag_sarg[DIAG_WAVES][2];
+template <class T>
+__device__ __forceinline__ void diag_sarg(int k, T v) {
+  const int w = (int)(blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64);
+  asm volatile("; scalar argument %0 landed" ::"s"(v));
+  const unsigned long long t = __builtin_amdgcn_s_memtime();
+  if ((threadIdx.x & 63) == 0 && w < DIAG_WAVES) g_diag_sarg[w][k] = t;
+}
+#define DIAG_SARG(k, v) diag_sarg(k, v)
 #define PH_INIT unsigned long long ph_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, ph_t = __builtin_amdgcn_s_memtime()
 #define PH(k) do { const unsigned long long ph_n = __builtin_amdgcn_s_memtime(); ph_acc[k] += ph_n - ph_t; ph_t = ph_n; } while (0)
 #define PH_STORE do { \
@@ -64,6 +76,9 @@ __device__ __forceinline__ void diag_stamp(int point) {
   int be_diag_hwid(unsigned int* hw) {                                                                \
     return hipMemcpyFromSymbol(hw, HIP_SYMBOL(g_diag_hw), sizeof(g_diag_hw)) == hipSuccess ? BE_OK : BE_E_HIP; \
   }                                                                                                   \
+  int be_diag_sarg(unsigned long long* cy) {                                                          \
+    return hipMemcpyFromSymbol(cy, HIP_SYMBOL(g_diag_sarg), sizeof(g_diag_sarg)) == hipSuccess ? BE_OK : BE_E_HIP; \
+  }                                                                                                   \
   int be_diag_clear(void) {                                                                           \
     static unsigned long long zero[DIAG_WAVES][DIAG_POINTS];                                          \
     if (hipMemcpyToSymbol(HIP_SYMBOL(g_diag_rt), zero, sizeof(zero)) != hipSuccess) return BE_E_HIP;  \
@@ -71,6 +86,7 @@ __device__ __forceinline__ void diag_stamp(int point) {
   }
 #else
 #define DIAG(pt) ((void)0)
+#define DIAG_SARG(k, v) ((void)0)
 #define PH_INIT ((void)0)
 #define PH(k) ((void)0)
 #define PH_STORE ((void)0)

@@ -8,6 +8,7 @@
 #include <vector>
 #include "ballenv.h"
 extern "C" int be_diag_stamps(unsigned long long* rt, unsigned long long* cy);
+extern "C" int be_diag_sarg(unsigned long long* cy);
 extern "C" int be_diag_clear(void);
 extern "C" int be_diag_hwid(unsigned int* hw);
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP %s at %d\n", hipGetErrorString(e), __LINE__); exit(1); } } while (0)
@@ -29,7 +30,7 @@ int main(int argc, char** argv) {
   be_reset(ctx, &st, nullptr, nullptr, 0, &out, nullptr);
   for (int k = 0; k < 300; ++k) be_step(ctx, &st, acts + (size_t)(k % 64) * N, nullptr, nullptr, &out, nullptr);
   CK(hipDeviceSynchronize());
-  std::vector<unsigned long long> rt(DW * DP), cy(DW * DP);
+  std::vector<unsigned long long> rt(DW * DP), cy(DW * DP), sa(DW * 2);
   for (int rep = 0; rep < 3; ++rep) {
     // rep 0: one cold launch after a sync; reps 1, 2: the last of 20 back-to-back launches
     be_diag_clear();
@@ -37,6 +38,7 @@ int main(int argc, char** argv) {
       be_step(ctx, &st, acts + (size_t)((rep * 20 + k) % 64) * N, nullptr, nullptr, &out, nullptr);
     CK(hipDeviceSynchronize());
     be_diag_stamps(rt.data(), cy.data());
+    be_diag_sarg(sa.data());
     int waves = 0; unsigned long long t0 = ~0ull, t1 = 0;
     for (int w = 0; w < DW; ++w) if (rt[w * DP + 0]) { waves++; t0 = std::min(t0, rt[w * DP + 0]); t1 = std::max(t1, rt[w * DP + 6]); }
     std::vector<double> start, endt; std::vector<std::vector<double>> ph(6);
@@ -72,6 +74,18 @@ int main(int argc, char** argv) {
     const char* names[6] = {"entry->barrier1 (loads)", "barrier1->physics", "physics->reset list", "list->stage written", "stage->after coop reset", "coop reset->end(copy)"};
     for (int p = 0; p < 6; ++p)
       printf("  %-26s cycles p50 %8.0f p90 %8.0f p99 %8.0f max %8.0f\n", names[p], pct(ph[p], .5), pct(ph[p], .9), pct(ph[p], .99), pct(ph[p], 1));
+    {   // step2_kernel's prologue: when the kernel arguments it loads through are in SGPRs
+      std::vector<std::vector<double>> pr(3);
+      for (int w = 0; w < DW; ++w) {
+        const unsigned long long c0 = cy[w * DP], c1 = cy[w * DP + 1], s0 = sa[w * 2], s1 = sa[w * 2 + 1];
+        if (!rt[w * DP + 0] || !(s0 >= c0 && s1 >= s0 && c1 >= s1)) continue;
+        pr[0].push_back((double)(s0 - c0)); pr[1].push_back((double)(s1 - c0)); pr[2].push_back((double)(c1 - s1));
+      }
+      const char* pn[3] = {"  entry->kernarg landed", "  entry->last scalar arg", "  last scalar arg->barrier1"};
+      for (int p = 0; p < 3; ++p)
+        if (!pr[p].empty())
+          printf("  %-26s cycles p50 %8.0f p90 %8.0f p99 %8.0f max %8.0f\n", pn[p], pct(pr[p], .5), pct(pr[p], .9), pct(pr[p], .99), pct(pr[p], 1));
+    }
     std::vector<std::vector<double>> sub(5);
     for (int w = 0; w < DW; ++w) {
       const unsigned long long* c = &cy[w * DP];
