@@ -4,7 +4,10 @@
 
 Translation units, compiled separately (each embeds its own gfx950 code
 object) and linked into one shared library:
-  csrc/ballenv.hip  step / reset / observe kernels + the C ABI
+  csrc/ballenv.hip  the step engine's kernels (step / reset / observe, the fused rollouts, the
+                    autoreset pool's fill) and their dispatcher
+  csrc/abi.hip      be_ctx and the step engine's C entry points (no kernels; step_types.h is the
+                    interface between the two)
   csrc/policy.hip   select_action kernel (-fno-slp-vectorize: scalar f32 FMAs
                     interleave better with MFMAs than SLP-packed ones on gfx950)
   csrc/features.hip sibling observation formats (prep_state2 block counts)
@@ -34,9 +37,9 @@ VGPR_MFMA = ["-mllvm", "-amdgpu-mfma-vgpr-form"]
 # SGPRs at wave launch instead of through a scalar load from the kernarg segment (step2_kernel's
 # prologue); the compiler keeps an s_load entry for firmware without the preload.
 KARG_PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
-UNITS = {"ballenv.hip": [*VGPR_MFMA, *KARG_PRELOAD], "policy.hip": ["-fno-slp-vectorize", *VGPR_MFMA], "features.hip": [], "board.hip": [],
-         "a2c.hip": []}
-HEADERS = [HDR, *(os.path.join(CSRC, h) for h in ("philox.h", "internal.h", "policy_core.h", "diag.h"))]
+UNITS = {"ballenv.hip": [*VGPR_MFMA, *KARG_PRELOAD], "abi.hip": [], "policy.hip": ["-fno-slp-vectorize", *VGPR_MFMA],
+         "features.hip": [], "board.hip": [], "a2c.hip": []}
+HEADERS = [HDR, *(os.path.join(CSRC, h) for h in ("philox.h", "internal.h", "policy_core.h", "diag.h", "step_types.h"))]
 
 
 def _stale(out, deps):

@@ -1,4 +1,4 @@
-// ballenv.hip -- MI355X (gfx950) batched BallEnv step engine + its C ABI.
+// ballenv.hip -- MI355X (gfx950) batched BallEnv step engine: the kernels and their dispatcher.
 //
 // One thread per env; the env index is the unit-stride (coalesced) HBM axis of
 // every state array (include/ballenv.h).  One launch of be_kernel<W, STEP>
@@ -38,127 +38,33 @@
 // Everything is integer except the reward path, which is f64 with the same
 // operation order as the reference (correctly rounded sqrt/div, no FMA
 // contraction: built with -ffp-contract=off), so results are bit-exact.
+//
+// This file is the step engine's one device translation unit: the device helpers, the reference's
+// rules, the kernels (one section each) and their dispatcher.  The types and the dispatch interface
+// are in step_types.h; be_ctx and the C entry points are in abi.hip, which names no kernel.
 #include <type_traits>
 #include <hip/hip_runtime.h>
 
 #include <math.h>
-#include <algorithm>
-#include <mutex>
-#include <new>
 #include <stdint.h>
 #include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 
 #include "ballenv.h"
-#include "internal.h"
 #include "philox.h"
 #include "policy_core.h"
+#include "step_types.h"
 
 namespace {
+
+using namespace bestep;
 
 // Philox purposes (counter word 3, high byte); oracle/ballenv_oracle.c uses the same.
 constexpr uint32_t PURPOSE_STEP_OBS = 1, PURPOSE_ACTION = 2, PURPOSE_RESET = 3, PURPOSE_SAMPLE = 4;
 constexpr int REJECT_LIMIT = 4096;
 constexpr int CS = 16;  // static obstacles per register chunk
 constexpr int CD = 8;   // dynamic obstacles per register chunk
-constexpr int HW_MAX = 63;   // largest collision radius R with a half-width table
 
-enum Mode { MODE_STEP = 0, MODE_RESET = 1, MODE_OBSERVE = 2 };
-
-// Per-context tables: a device buffer staged into LDS once per block.
-struct Tables {
-  int32_t goal[BE_MAX_GOALS];                 // packed goal xy
-  int32_t action[BE_MAX_ACTIONS];             // packed (dx, dy)
-  int32_t speed[BE_MAX_DYNAMIC];              // obstacle_speed
-  int32_t strip_obs_x, strip_obs_y, strip_goal_x, strip_goal_y, strip_agent_x, strip_agent_y;
-  int32_t radius_obstacle, radius_agent;
-  uint8_t n_other[BE_MAX_GOALS];              // goals with a different value than goal g
-  uint8_t other[BE_MAX_GOALS][BE_MAX_GOALS];  // pick -> goal index, per current goal g (newGoalList)
-  uint8_t hw[HW_MAX + 1];                     // floor(sqrt(R^2 - d^2)), d = 0..R (only when R <= HW_MAX)
-};
-
-// The fixed-shape step kernels' 64-bit row-span table (span_fits: W-1+2R <= 63): span[j] holds the cells an obstacle
-// at window column C = W-1+R lights in a row at distance |j - J0| (J0 = R+K-1): bits C-hw .. C+hw,
-// 0 past R.  A near entry at window (f, e) lights row k with span[e - k + J0] >> (C - f), clipped to
-// W bits -- one LDS read, one shift and one OR per row (raster_rows_span).  It follows Tables in the
-// same device buffer; only the fixed-shape step kernels stage it.
-constexpr int SPAN_N = 72;
-struct TablesX {
-  Tables t;
-  uint64_t span[SPAN_N];
-};
-static_assert(sizeof(Tables) % 16 == 0 && sizeof(TablesX) % 16 == 0, "16-byte table staging");
-__host__ __device__ constexpr bool span_fits(int W, int R) {   // W >= 2: K = W-1 rows, J0 = R+W-2
-  return W >= 2 && R >= 0 && W - 1 + 2 * R <= 63 && 2 * R + 2 * (W - 1) - 1 <= SPAN_N;
-}
-
-// Kernel arguments: hot fields first, 64-byte lines (see the latency notes above).
-struct KParams {
-  // line 0
-  int32_t* agent; int32_t* goal; double* prev_dist; double* total_dist;
-  double* ep_return; int32_t* ep_len; uint32_t* episode; int32_t* static_obs;
-  // line 1
-  int32_t* dyn_obs; uint8_t* dyn_goal; uint8_t* obs; float* obs_f32;
-  double* reward; uint8_t* done; const uint8_t* actions; const Tables* tables;
-  // line 2
-  int32_t n, window, ns, nd, R, speed_x, speed_y, screen_w;
-  int32_t screen_h, goal_change, certainty, time_limit, num_actions, autoreset, gid0, dbg;
-  // line 3
-  double threshold_goal, time_penalty, static_penalty, dynamic_penalty, min_spawn_dist;
-  double inv_g1;               // 1 / (goal_change + 1): counter = ep_len mod (G+1) without an integer divide
-  unsigned long long seed;
-  int* status;
-  // line 4 (cold)
-  const int16_t* deltas; const int16_t* tape; const uint8_t* mask; const int16_t* reset_tape;
-  uint8_t* truncated; uint8_t* terminal_obs; double* final_return; int32_t* final_len;
-  // line 5 (cold)
-  double* stats;               // (slots, 8): one slot per wave / block of the step kernel (be_stats_slots)
-  int32_t reset_tape_len;
-  int32_t min_spawn_d2;        // integer d2: sqrt(d2) < min_spawn_dist  <=>  d2 < min_spawn_d2
-  // fixed-shape kernels only (pick_kernel checks the preconditions):
-  uint32_t amx, amy;           // action a's (dx+1, dy+1) at bits 2a..2a+1 (every move in {-1,0,1})
-  int32_t num_goals;           // goals pairwise distinct: newGoalList(g)[pick] = pick + (pick >= g)
-  int32_t prev_read;           // 1: read prev_dist; 0 (A/B only, when no reset can re-sample the agent,
-                               // Q9): prev_dist == calc_dist(goal, agent), recomputed
-  int32_t steps;               // rollout_kernel: steps per launch (actions / outputs are (steps, N, ...))
-  // fused policy rollouts (rollout_kernel with HT > 0, be_policy_rollout)
-  int32_t pol_bytes, pol_actions;
-  const uint8_t* pol_img;      // packed Policy(W) image (policy_core.h PolLayout)
-  const uint8_t* obs_in;       // (N, F) obs of the current state: step 0's policy input
-  uint8_t* obs_last;           // (N, F) obs after the last step, or NULL
-  uint8_t* act_out; float* logp_out; float* value_out;   // (steps, N)
-  unsigned long long pol_seed;
-  // the autoreset pool (layout below; nullptr: every reset is drawn inline)
-  uint32_t* pool;
-};
-
-// ------------------------------------------------------------------ the autoreset pool
-// A reset in Philox mode is a pure function of (seed, global env id, new episode) and the context's
-// config (reset_env_philox's counter layout), so it can be drawn before the env finishes.
-// pool_fill_kernel draws, for every env at episode e, the resets into episodes e+1 and e+2; the step
-// kernels (step2_kernel, stepw_kernel) copy the entry of episode e+1 when the env finishes, instead
-// of running the reset's Philox chains on the wave's critical path, and fall back to the inline
-// wave_resets pass when the entry is stale (its tag is not e+1: the env reset twice since the last
-// fill, or no fill ran).  Two entries per env, slot = episode & 1 (entry index x = slot * N + env),
-// everything addressed from the one base p.pool (a uniform pointer + a 32-bit byte offset + an
-// immediate: no per-array base pointers to keep in SGPRs):
-//   tags    uint2 [2N] at byte 0:      (the episode the entry resets into, flags: POOL_VALID written,
-//                                      POOL_REJ a rejection loop hit its bound) -- the fill's scan
-//                                      reads these 8 bytes per entry, coalesced
-//   bodies  112 B [2N] at byte 16 N:   the entry itself, contiguous (a consuming lane reads it with
-//                                      seven 16-byte loads):
-//     w0..2  ROWS: the reset obs's distinct window rows, packed as the consuming kernel ORs them
-//            (W = 10: three rows per word at bits 10 r; W = 5: four rows at bits 5 r, in w0)
-//     w3 AGENT, w4 GOAL (packed xy), w5 unused, w6..7 PREV f64 (state[2], the pre-resample distance,
-//     Q9), w8..9 TOTAL f64, w10.. the NS statics' then the ND dynamics' packed xy (a reset's dyn_goal
-//     is k)
-constexpr uint32_t POOL_VALID = 1u, POOL_REJ = 2u;
-constexpr int PB_ROWS = 0, PB_AGENT = 3, PB_GOAL = 4, PB_PREV = 6, PB_TOTAL = 8, PB_OBS = 10;
-__host__ __device__ constexpr int pool_body_words(int ns, int nd) { return (PB_OBS + ns + nd + 3) & ~3; }
-__host__ __device__ constexpr int64_t pool_bytes_per_env(int ns, int nd) { return 2 * (8 + 4ll * pool_body_words(ns, nd)); }
-static_assert(pool_body_words(13, 5) == 28, "the fixed-shape kernels' 112-byte entry body");
-// byte offset of word w of entry x's body (N <= 2^22 keeps every offset below 2^32: pool_max_envs)
+// byte offset of word w of entry x's body (N <= 2^22 keeps every offset below 2^32: POOL_MAX_ENVS)
 __device__ __forceinline__ uint32_t pool_body(uint32_t n, uint32_t x, int nbw) { return 16u * n + x * (4u * (uint32_t)nbw); }
 // T at byte off + imm of the pool: the uniform base + zext(32-bit offset) + an immediate, so the
 // access is one global load / store with the immediate in its offset field
@@ -170,24 +76,10 @@ template <class T>
 __device__ __forceinline__ void pool_st(uint32_t* pool, uint32_t off, T v, uint32_t imm = 0) {
   *reinterpret_cast<T*>(reinterpret_cast<char*>(pool) + (size_t)off + imm) = v;
 }
-// BE_POOL_MODE (A/B): where stepw_kernel loads the pool entries of its finished envs (step2_kernel
-// loads them at the head of its finishing path, which only the waves with a finished env run).
-//   1: right after done is known, before the physics stores, waited for inside that (divergent)
-//      branch -- only the waves with a finished env wait;
-//   5: inside the reset section (the uniform `if (m)` of the waves with a finished env), after the
-//      stores: the rest of the kernel is the pre-pool code.
-// (Measured and dropped: the loads unwaited in the branch -- the waitcnt pass then drains every
-// outstanding store at the merge before the reset loop, in every wave; branch-free buffer loads with
-// an out-of-range offset for the lanes without a finished env; the loads after the stores outside the
-// reset section.  profiles/r06_pool_ab.txt)
-#ifndef BE_POOL_MODE
-#define BE_POOL_MODE 1
-#endif
 __device__ __forceinline__ uint32_t u4w(const uint4& v, int k) { return k == 0 ? v.x : k == 1 ? v.y : k == 2 ? v.z : v.w; }
 __device__ __forceinline__ double u2d(uint32_t lo, uint32_t hi) {
   return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
-constexpr int64_t POOL_MAX_ENVS = 1ll << 22;
 
 // Diagnostics hooks (DBG skip bits, DIAG / PH phase stamps): no-ops in the release build; a
 // -DBE_DIAG_STAMPS / -DBE_DIAG_SKIP build (tools/build_diag.sh, tools/build_ab_lib.sh) defines them.
@@ -212,24 +104,7 @@ __device__ __forceinline__ T ld_s(const T* base, uint32_t idx) {
 }
 // Output / state stores of the fixed-shape step kernels: write-through (sc1, a relaxed agent-scope
 // atomic store), so the stores drain while the wave runs instead of in the kernel-end L2 write-back.
-// step2_kernel's finishing path (A/B; us per launch at 65 536 / 32 768 envs, the parent 5.66-5.69 /
-// 4.59-4.60: profiles/r07_step2_finish_path_ab.txt)
-//   BE_S2_FIN_LOAD   1: every lane loads its own env's pool entry, no branch, not waited for;
-//                    0: only the finishing lanes, in their branch, waited in place (5.73-5.89 / 4.85-5.00)
-//   BE_S2_FIN_ORDER  the episode-statistics fold: 1 before the raster (5.49-5.52 / 4.68-4.69),
-//                    2 between the raster and the entry wait (5.64-5.67 / 4.81-4.82),
-//                    3 after the copy-out, off the path to the wave's last obs store (5.39-5.42 / 4.51)
-#ifndef BE_S2_FIN_LOAD
-#define BE_S2_FIN_LOAD 1
-#endif
-#ifndef BE_S2_FIN_ORDER
-#define BE_S2_FIN_ORDER 3
-#endif
-#ifndef BE_S2_CT
-#define BE_S2_CT 256        // step2_kernel: threads per block (A/B)
-#endif
-constexpr int S2_CT = BE_S2_CT;
-// copy-out store kinds: the step kernels write through (sc1); the fused rollouts' per-step obs rows
+// Copy-out store kinds: the step kernels write through (sc1); the fused rollouts' per-step obs rows
 // are plain stores (sc1 there measured no faster)
 constexpr int ST_PLAIN = 0, ST_WT = 1;
 template <class T>
@@ -669,9 +544,9 @@ __device__ void reset_env(const KParams& p, const Tables& t, int i, ResetDraws& 
   }
 }
 
-// Perf-mode (Philox) reset, split over the env's LPE lanes.  Each quantity has its
-// own counter, so the lanes draw in parallel and nothing is serial but the
-// (rare) agent re-sample loop:
+// Perf-mode (Philox) reset on the env's own lane.  Each quantity has its own counter, so the
+// cooperative paths (be_kernel's block list, wave_resets) draw them in parallel from the same
+// layout and nothing is serial but the (rare) agent re-sample loop:
 //   sub = 0                         words gx, gy, ax, ay
 //   sub = 1 + r                     agent re-sample r: words ax, ay
 //   sub = 1<<22 | k<<12 | a         static obstacle k, attempt a: words x, y
@@ -679,8 +554,8 @@ __device__ void reset_env(const KParams& p, const Tables& t, int i, ResetDraws& 
 // Distributions and rejection rules are the reference's (ballenv_env.py:113-167);
 // only the order in which the random words are consumed differs from numpy's
 // single stream, which the tape mode (reset_env) reproduces exactly.
-template <int BLOCK, int LPE>
-__device__ void reset_env_philox(const KParams& p, const Tables& t, int i, int q, uint32_t gid, uint32_t episode,
+template <int BLOCK>
+__device__ void reset_env_philox(const KParams& p, const Tables& t, int i, uint32_t gid, uint32_t episode,
                                  int& ax, int& ay, int& gx, int& gy, NearList<BLOCK>& nl) {
   const int N = p.n, W = p.screen_w, H = p.screen_h;
   const u4 b0 = philox(gid, episode, 0u, tag(PURPOSE_RESET, 0), p.seed);
@@ -690,24 +565,22 @@ __device__ void reset_env_philox(const KParams& p, const Tables& t, int i, int q
   ay = map_range(b0.w, 0, t.strip_agent_y);
   const double dist = calc_dist(gx, gy, ax, ay);
   for (int r = 0; calc_dist(gx, gy, ax, ay) < p.min_spawn_dist; ++r) {
-    if (r >= REJECT_LIMIT - 1) { if (q == 0) atomicOr(p.status, BE_STATUS_REJECTION_LIMIT); break; }
+    if (r >= REJECT_LIMIT - 1) { atomicOr(p.status, BE_STATUS_REJECTION_LIMIT); break; }
     const u4 b = philox(gid, episode, 0u, tag(PURPOSE_RESET, 1 + r), p.seed);
     ax = map_range(b.x, 0, t.strip_agent_x);
     ay = map_range(b.y, 0, t.strip_agent_y);
   }
-  if (q == 0) {
-    p.agent[i] = pk(ax, ay);
-    p.goal[i] = pk(gx, gy);
-    p.prev_dist[i] = dist;  // pre-resample distance (Q9)
-    p.total_dist[i] = calc_dist(ax, ay, gx, gy);
-    p.ep_return[i] = 0.0;
-    p.ep_len[i] = 0;
-    p.episode[i] = episode;
-  }
+  p.agent[i] = pk(ax, ay);
+  p.goal[i] = pk(gx, gy);
+  p.prev_dist[i] = dist;  // pre-resample distance (Q9)
+  p.total_dist[i] = calc_dist(ax, ay, gx, gy);
+  p.ep_return[i] = 0.0;
+  p.ep_len[i] = 0;
+  p.episode[i] = episode;
   const Win g(p, ax, ay);
   nl.cnt = 0;
   const int rx = t.radius_obstacle + t.radius_agent, ry2 = t.radius_obstacle + 2 * t.radius_agent;
-  for (int k = q; k < p.ns; k += LPE) {
+  for (int k = 0; k < p.ns; ++k) {
     int ox = 0, oy = 0;
     for (int a = 0;; ++a) {
       const u4 b = philox(gid, episode, 0u, tag(PURPOSE_RESET, (1u << 22) | ((uint32_t)k << 12) | (uint32_t)a), p.seed);
@@ -722,7 +595,7 @@ __device__ void reset_env_philox(const KParams& p, const Tables& t, int i, int q
     int f, e;
     if (g.near(ox, oy, f, e)) nl.push(f, e);
   }
-  for (int k = q; k < p.nd; k += LPE) {
+  for (int k = 0; k < p.nd; ++k) {
     const u4 b = philox(gid, episode, 0u, tag(PURPOSE_RESET, (2u << 22) | ((uint32_t)k << 12)), p.seed);
     const int ox = map_range(b.x, t.strip_obs_x, W - t.strip_obs_x);
     const int oy = map_range(b.y, t.strip_obs_y, H - t.strip_obs_y);
@@ -778,26 +651,6 @@ __device__ __forceinline__ void wave_stats2(bool done, double ret, int len, Wave
   }
 }
 
-// ------------------------------------------------------------------ lane groups
-// LPE lanes cooperate on one env: obstacle k belongs to lane k % LPE, obs word w to lane w % LPE.
-constexpr int BLOCK_THREADS = 256;
-template <int LPE>
-__device__ __forceinline__ uint32_t group_or(uint32_t x) {
-  static_assert(LPE == 1 || LPE == 2 || LPE == 4, "LPE must be 1, 2 or 4");
-  if constexpr (LPE >= 2) x |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0xB1, 0xF, 0xF, false);  // quad_perm 1,0,3,2
-  if constexpr (LPE >= 4) x |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x4E, 0xF, 0xF, false);  // quad_perm 2,3,0,1
-  return x;
-}
-template <int LPE>
-__device__ __forceinline__ int group_bcast(int x) {  // value of the group's lane 0
-  if constexpr (LPE == 1) return x;
-  else if constexpr (LPE == 2) return __builtin_amdgcn_update_dpp(0, x, 0xA0, 0xF, 0xF, false);  // quad_perm 0,0,2,2
-  else return __builtin_amdgcn_update_dpp(0, x, 0x00, 0xF, 0xF, false);                          // quad_perm 0,0,0,0
-}
-
-constexpr int lanes_for(int) { return 1; }   // the generic kernel: one lane per env
-constexpr int envs_per_block(int WT) { return BLOCK_THREADS / lanes_for(WT); }
-constexpr int RCAP = 64;  // resets handled per cooperative pass (more loop)
 
 // One dynamic obstacle's move_obstacles (ballenv_env.py:323-353), branch-free.
 // Tape mode: t0/t1 are the values of its first/second randint call.  Philox mode:
@@ -1099,10 +952,53 @@ __device__ void wave_resets(const KParams& p, const Tables& t, unsigned long lon
   }
 }
 
+// ------------------------------------------------------------------ the step's rules
+// What BallEnv.step decides per env, once.  The step kernels differ in where they call these and in
+// where the operands come from (KParams, KHot, a value computed early), so the helpers take values,
+// not KParams.  The config operands are taken by reference: each is then read where the inline text
+// read it, not ahead of the call, which keeps the kernels' instruction schedules.  A helper is used
+// at a site only where the kernel's machine code stays what it was (profiles/r09_refactor_isa.txt
+// lists the sites that keep their inline text; each says so in a comment).
+
+// The dynamic obstacles' goal-change counter (ballenv_env.py:323-353): every obstacle's counter
+// starts at 0 on reset and runs 0..G, so it is ep_len mod (G+1), here through inv_g1 = 1 / (G+1)
+// without an integer divide; the obstacles re-pick their goals on the step where it reaches G.
+// (const references on purpose -- see above; by value the kernels' instruction order changes)
+__device__ __forceinline__ int goal_counter(int len, const int& goal_change, const double& inv_g1) {
+  int counter = (int)((double)len * inv_g1);
+  counter = len - counter * (goal_change + 1);
+  if (counter < 0) counter += goal_change + 1;
+  if (counter > goal_change) counter -= goal_change + 1;
+  return counter;
+}
+
+// Action a's unit move (ballenv_env.py:247-259) from the packed tables (KParams::amx / amy: dx+1,
+// dy+1 at bits 2a..2a+1); an index past num_actions raises BE_STATUS_BAD_ACTION and moves as action 0.
+// (const references on purpose, as goal_counter's)
+__device__ __forceinline__ void unit_move(int a, const int& num_actions, const uint32_t& amx, const uint32_t& amy,
+                                          int& dx, int& dy, uint32_t& flags) {
+  flags |= a >= num_actions ? (uint32_t)BE_STATUS_BAD_ACTION : 0u;
+  const uint32_t sh = 2u * (uint32_t)(a < num_actions ? a : 0);
+  dx = (int)((amx >> sh) & 3u) - 1; dy = (int)((amy >> sh) & 3u) - 1;
+}
+
+// The collision penalty (calculate_reward, ballenv_env.py:200-229): the first hit in obstacle_list
+// counts, and the statics come first in it (Q3).
+// (const references on purpose, as goal_counter's)
+__device__ __forceinline__ double collision_penalty(double reward, bool hs, bool hd, const double& static_penalty,
+                                                    const double& dynamic_penalty) {
+  if (hs) reward -= static_penalty;
+  else if (hd) reward -= dynamic_penalty;
+  return reward;
+}
+
+// The end of a step (env_done / trunc / done) and the wave's status OR + publish are the same text in all
+// five step kernels and have no helper: every form tried moved instructions in every kernel.
+
 // ------------------------------------------------------------------ the kernel
 // MODE_STEP: physics + (autoreset) + obs.  MODE_RESET: reset masked envs + obs.
 // MODE_OBSERVE: obs only.  WT = compile-time W (0 = runtime W: no LDS staging,
-// sequential resets).  LPE = lanes per env.
+// sequential resets).  One lane per env.
 //
 // Resets (Philox mode) are block-cooperative: envs that must reset are compacted
 // into an LDS list, then phase A draws each one's goal/agent (one thread per env)
@@ -1113,6 +1009,17 @@ __device__ void wave_resets(const KParams& p, const Tables& t, unsigned long lon
 // NSC/NDC > 0: a step kernel specialised for exactly NSC static / NDC dynamic obstacles in
 // Philox mode (no tape), one lane per env -- every obstacle loop is unrolled to its exact
 // trip count (the dispatcher picks it only for a matching config).
+constexpr int RCAP = 64;  // resets handled per cooperative pass (more loop)
+// be_kernel's dynamic LDS, the one source of its offsets and of the launch's byte count:
+//   [near lists: nobs+1 slots x 256 lanes x 4 B][obs stage: 256 envs x F bytes (compile-time W only)]
+// (+1 slot: the predicated pushes write one slot ahead)
+struct BeLds {
+  __host__ __device__ static constexpr size_t stage(int nobs) { return (size_t)(nobs + 1) * BLOCK_THREADS * 4; }
+  __host__ __device__ static constexpr int bytes(int nobs, int WT) {   // WT = 0: run-time W, no stage
+    return ((nobs + 1) * BLOCK_THREADS * 4 + (WT > 0 ? BLOCK_THREADS * (4 + WT * WT) : 0) + 15) & ~15;
+  }
+};
+static_assert(BeLds::bytes(18, 10) == 46080 && BeLds::bytes(18, 5) == 26880, "the default shapes' LDS (one-lane fixed and generic)");
 __device__ __forceinline__ Tables& tab_of(TablesX& x) { return x.t; }
 __device__ __forceinline__ Tables& tab_of(Tables& x) { return x; }
 // be_kernel's rasteriser: FIXED from the wave's span table when it fits R (a uniform branch),
@@ -1134,10 +1041,9 @@ template <int WT, int MODE, int NSC = 0, int NDC = 0, bool POOL = false>
 __global__ __launch_bounds__(BLOCK_THREADS) void be_kernel(KParams p) {
   constexpr bool FIXED = NSC > 0 || NDC > 0;
   static_assert(!POOL || (FIXED && MODE == MODE_STEP && (WT == 10 || WT == 5)), "the pool: fixed-shape steps at W = 10 / 5");
-  constexpr int LPE = FIXED ? 1 : lanes_for(WT);
-  constexpr int EPB = BLOCK_THREADS / LPE;
+  constexpr int EPB = BLOCK_THREADS;   // envs per block: one lane per env
   static_assert(!FIXED || (MODE == MODE_STEP && WT > 0 && NSC <= CS && NDC <= CD), "fixed-shape kernels: step only");
-  constexpr int SPL = FIXED ? NSC : CS / LPE, DPL = FIXED ? NDC : CD / LPE;   // obstacle slots per lane
+  constexpr int SPL = FIXED ? NSC : CS, DPL = FIXED ? NDC : CD;   // obstacle register slots
   constexpr bool COOP = WT > 0;                   // cooperative reset path (needs compile-time W)
   constexpr int KR = WT > 0 ? Geo<WT>::K : 1;
   extern __shared__ __align__(16) uint8_t smem[];
@@ -1166,16 +1072,12 @@ __global__ __launch_bounds__(BLOCK_THREADS) void be_kernel(KParams p) {
   const int N = p.n, Ns = FIXED ? NSC : p.ns, Nd = FIXED ? NDC : p.nd;
   const int tid = threadIdx.x;
   Tables& t = tab_of(t_blk[FIXED ? (tid >> 6) : 0]);
-  const int q = tid & (LPE - 1);                  // lane within the env's group
-  const int el = tid / LPE;                        // env within the block
   const int blk0 = (int)blockIdx.x * EPB;
-  const int i = blk0 + el;
+  const int i = blk0 + tid;
   const bool valid = i < N;
-  const bool lead = q == 0;                        // the group lane that owns per-env stores
 
-  // LDS: [near lists: nobs+1 slots x 256 lanes x 4 B][obs stage: EPB x F bytes]
-  NearList<BLOCK_THREADS> nl{reinterpret_cast<uint32_t*>(smem) + tid, 0};
-  uint8_t* stage = smem + (size_t)(Ns + Nd + 1) * BLOCK_THREADS * 4;
+  NearList<BLOCK_THREADS> nl{reinterpret_cast<uint32_t*>(smem) + tid, 0};   // (BeLds)
+  uint8_t* stage = smem + BeLds::stage(Ns + Nd);
 
   int ax = 0, ay = 0, gx = 0, gy = 0;
   bool done = false;
@@ -1245,7 +1147,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void be_kernel(KParams p) {
       if (nd0 > 0) {
 #pragma unroll
         for (int j = 0; j < DPL; ++j) {
-          const int k = min(q + LPE * j, nd0 - 1);
+          const int k = min(j, nd0 - 1);
           dp[j] = (p.dyn_obs + (size_t)k * N)[i];
           dgi[j] = (p.dyn_goal + (size_t)k * N)[i];
           if (!FIXED && p.tape) { t0[j] = (p.tape + (size_t)(2 * k) * N)[i]; t1[j] = (p.tape + (size_t)(2 * k + 1) * N)[i]; }
@@ -1254,7 +1156,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void be_kernel(KParams p) {
       // fixed slots: indices past the count re-read the last obstacle (same lines: no extra traffic)
       if (ns0 > 0) {
 #pragma unroll
-        for (int j = 0; j < SPL; ++j) so[j] = (p.static_obs + (size_t)min(q + LPE * j, ns0 - 1) * N)[i];
+        for (int j = 0; j < SPL; ++j) so[j] = (p.static_obs + (size_t)min(j, ns0 - 1) * N)[i];
       }
       old_dist = p.prev_dist[i];
       total = p.total_dist[i];
@@ -1270,7 +1172,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void be_kernel(KParams p) {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   } else {
     if (tid < TW) reinterpret_cast<uint32_t*>(&t)[tid] = tword[0].x;
-    if (EPB == BLOCK_THREADS || tid < EPB) s_slot_of[tid] = -1;
+    s_slot_of[tid] = -1;
     if (tid == 0) s_nreset = 0;
     __syncthreads();  // barrier 1: tables staged (the state loads retire in order as they are used)
   }
@@ -1287,11 +1189,9 @@ __global__ __launch_bounds__(BLOCK_THREADS) void be_kernel(KParams p) {
   if (valid) {
     gx = px(goal0); gy = py(goal0);
     if (MODE == MODE_STEP) {
-      // ---- action -> agent move + clamp (ballenv_env.py:247-259); every lane of the group
+      // ---- action -> agent move + clamp (ballenv_env.py:247-259)
       if (FIXED) {   // unit moves from the packed kernel-argument table: no LDS round trip
-        st_flags |= a >= p.num_actions ? (uint32_t)BE_STATUS_BAD_ACTION : 0u;
-        const uint32_t sh = 2u * (uint32_t)(a < p.num_actions ? a : 0);
-        dx = (int)((p.amx >> sh) & 3u) - 1; dy = (int)((p.amy >> sh) & 3u) - 1;
+        unit_move(a, p.num_actions, p.amx, p.amy, dx, dy, st_flags);
       } else if (p.actions) {
         st_flags |= a >= p.num_actions ? (uint32_t)BE_STATUS_BAD_ACTION : 0u;
         a = a < p.num_actions ? a : 0;
@@ -1308,12 +1208,8 @@ __global__ __launch_bounds__(BLOCK_THREADS) void be_kernel(KParams p) {
       bool hs = false, hd = false;
       DIAG(8);
 
-      // ---- dynamic obstacles: move (counter == ep_len mod (G+1): all start at 0 on reset)
-      int counter = (int)((double)len0 * p.inv_g1);
-      counter = len0 - counter * (p.goal_change + 1);
-      if (counter < 0) counter += p.goal_change + 1;
-      if (counter > p.goal_change) counter -= p.goal_change + 1;
-      const bool change = counter >= p.goal_change;
+      // ---- dynamic obstacles
+      const bool change = goal_counter(len0, p.goal_change, p.inv_g1) >= p.goal_change;
       const bool tape = !FIXED && p.tape != nullptr;
       // Philox fields: obstacle k uses 24-bit field k%5 of block k/5 (both of its draws).
       uint32_t wj[DPL];
@@ -1324,10 +1220,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void be_kernel(KParams p) {
         u4 b1{0u, 0u, 0u, 0u};
         if (nd0 > 5) b1 = philox(gid, episode, (uint32_t)len0, tag(PURPOSE_STEP_OBS, 1u), p.seed);
 #pragma unroll
-        for (int j = 0; j < DPL; ++j) {
-          const int k = q + LPE * j;   // < CD = 8 <= 10: blocks 0 and 1 cover every slot
-          wj[j] = k < 5 ? pick_field(b0, k) : pick_field(b1, k - 5);
-        }
+        for (int j = 0; j < DPL; ++j) wj[j] = j < 5 ? pick_field(b0, j) : pick_field(b1, j - 5);   // (CD = 8 <= 10: two blocks cover every slot)
       }
       // FIXED: exact trip counts; one (dx, dy) per obstacle feeds both the collision test and
       // the window-box test (the box is a superset of the cells' R-neighbourhood; the
@@ -1384,19 +1277,18 @@ __global__ __launch_bounds__(BLOCK_THREADS) void be_kernel(KParams p) {
       constexpr int FAR = -30000;
 #pragma unroll
       for (int j = 0; j < (FIXED ? 0 : DPL); ++j) {
-        const int k = q + LPE * j;
-        const bool real = k < nd0;
+        const bool real = j < nd0;
         int ox = real ? px(dp[j]) : FAR, oy = real ? py(dp[j]) : FAR;
         if (!DBG(DBG_NO_DYN) && real) {
-          const int ng = dyn_move(p, t, ox, oy, dgi[j], t.speed[k], change, tape, t0[j], t1[j], wj[j], st_flags);
-          (p.dyn_obs + (size_t)k * N)[i] = pk(ox, oy);
-          if (ng != dgi[j]) (p.dyn_goal + (size_t)k * N)[i] = (uint8_t)ng;
+          const int ng = dyn_move(p, t, ox, oy, dgi[j], t.speed[j], change, tape, t0[j], t1[j], wj[j], st_flags);
+          (p.dyn_obs + (size_t)j * N)[i] = pk(ox, oy);
+          if (ng != dgi[j]) (p.dyn_goal + (size_t)j * N)[i] = (uint8_t)ng;
         }
         hd |= collides(ox, oy, ax, ay, R2);
         int f, e;
         nl.push_if(nb.maybe(ox, oy) && g.near(ox, oy, f, e) && !DBG(DBG_NO_NEAR), f, e);
       }
-      for (int kb = CD + q; !FIXED && kb < Nd; kb += LPE) {  // configs with more than CD dynamic obstacles
+      for (int kb = CD; !FIXED && kb < Nd; ++kb) {  // configs with more than CD dynamic obstacles
         int32_t* pos = p.dyn_obs + (size_t)kb * N + i;
         uint8_t* gp = p.dyn_goal + (size_t)kb * N + i;
         int ox = px(*pos), oy = py(*pos);
@@ -1414,37 +1306,32 @@ __global__ __launch_bounds__(BLOCK_THREADS) void be_kernel(KParams p) {
       // ---- static obstacles: collision + near test
 #pragma unroll
       for (int j = 0; j < (FIXED ? 0 : SPL); ++j) {
-        const int k = q + LPE * j;
-        const bool real = k < ns0;
+        const bool real = j < ns0;
         const int ox = real ? px(so[j]) : FAR, oy = real ? py(so[j]) : FAR;
         hs |= collides(ox, oy, ax, ay, R2);
         int f, e;
         nl.push_if(nb.maybe(ox, oy) && g.near(ox, oy, f, e) && !DBG(DBG_NO_NEAR), f, e);
       }
-      for (int kb = CS + q; !FIXED && kb < Ns; kb += LPE) {
+      for (int kb = CS; !FIXED && kb < Ns; ++kb) {
         const int32_t o = (p.static_obs + (size_t)kb * N)[i];
         const int ox = px(o), oy = py(o);
         hs |= collides(ox, oy, ax, ay, R2);
         int f, e;
         if (nb.maybe(ox, oy) && g.near(ox, oy, f, e)) nl.push(f, e);
       }
-      // the group's collision flags (every lane of a valid group is active here)
-      hs = group_or<LPE>((uint32_t)hs) != 0u;
-      hd = group_or<LPE>((uint32_t)hd) != 0u;
       DIAG(10);
 
       // ---- distance, reward, done (ballenv_env.py:268-286, 200-229)
       const double dist = calc_dist(gx, gy, ax, ay);
       double reward = 0.0 - p.time_penalty;
       reward += (old_dist - dist) / total;
-      if (hs) reward -= p.static_penalty;          // statics come first in obstacle_list (Q3)
-      else if (hd) reward -= p.dynamic_penalty;
+      reward = collision_penalty(reward, hs, hd, p.static_penalty, p.dynamic_penalty);
       ret += reward;
       const int len = len0 + 1;
       const bool env_done = (dist < p.threshold_goal) || hs || hd;
       const bool trunc = p.time_limit > 0 && len >= p.time_limit;
       done = env_done || trunc;
-      if (lead) {
+      {
         // FIXED: SGPR-base stores with 32-bit offsets (FIX_MAX_ENVS); the generic kernels index in 64 bits
         auto sto = [&](auto* base, auto v) {
           if constexpr (FIXED) st_ws(base, (uint32_t)i, v);
@@ -1480,9 +1367,9 @@ __global__ __launch_bounds__(BLOCK_THREADS) void be_kernel(KParams p) {
   // sums are not live across the pool's loads: 148 -> 107 VGPRs, four waves per SIMD again)
   if (!POOL && MODE == MODE_STEP && p.stats && !DBG(DBG_NO_STATS)) {   // all lanes converged here
     if constexpr (FIXED) {   // one slot per 32 envs (be_stats_slots): the wave's two halves
-      wave_stats2(done && lead, fin_ret, fin_len, ws, ws_hi);
+      wave_stats2(done, fin_ret, fin_len, ws, ws_hi);
     } else {
-      ws = wave_stats(done && lead, fin_ret, fin_len);
+      ws = wave_stats(done, fin_ret, fin_len);
     }
   }
 
@@ -1494,47 +1381,41 @@ __global__ __launch_bounds__(BLOCK_THREADS) void be_kernel(KParams p) {
   }
   const bool tape_reset = MODE == MODE_RESET && p.reset_tape != nullptr;
   if (valid && do_reset) {
-    if (MODE == MODE_STEP && p.terminal_obs) {  // obs of the terminal state (group-uniform branch)
+    if (MODE == MODE_STEP && p.terminal_obs) {  // obs of the terminal state
       const int F = 4 + p.window * p.window;
       const Win g(p, ax, ay);
       const int quad = quadrant(ax, ay, gx, gy);
       if constexpr (WT > 0) {
         uint32_t rows[Geo<WT>::K], flat[Geo<WT>::NW];
         raster_fixed<WT, FIXED>(nl, g, p.R, rows, t_blk[FIXED ? (tid >> 6) : 0]);
-#pragma unroll
-        for (int k = 0; k < Geo<WT>::K; ++k) rows[k] = group_or<LPE>(rows[k]);
         flatten<WT>(rows, flat);
-        if (lead) write_row_global<WT>(p.terminal_obs + (int64_t)i * F, flat, quad);
+        write_row_global<WT>(p.terminal_obs + (int64_t)i * F, flat, quad);
       } else {
         write_row_generic<BLOCK_THREADS>(nl, g, quad, p.terminal_obs + (int64_t)i * F, nullptr);
       }
     }
     if (!COOP || tape_reset) {
-      // sequential reset on the lead lane: the reference's single draw stream (tape), or runtime-W kernels
-      if (lead) {
-        ResetDraws ds{tape_reset ? p.reset_tape : nullptr, p.reset_tape_len, N, i, 0, gid, episode + 1u, p.seed,
-                      p.status};
-        if (tape_reset) reset_env<BLOCK_THREADS>(p, t, i, ds, ax, ay, gx, gy, nl);
-        else reset_env_philox<BLOCK_THREADS, 1>(p, t, i, 0, gid, episode + 1u, ax, ay, gx, gy, nl);
+      // sequential reset: the reference's single draw stream (tape), or runtime-W kernels
+      if (tape_reset) {
+        ResetDraws ds{p.reset_tape, p.reset_tape_len, N, i, 0, gid, episode + 1u, p.seed, p.status};
+        reset_env<BLOCK_THREADS>(p, t, i, ds, ax, ay, gx, gy, nl);
       } else {
-        nl.cnt = 0;
+        reset_env_philox<BLOCK_THREADS>(p, t, i, gid, episode + 1u, ax, ay, gx, gy, nl);
       }
-      ax = group_bcast<LPE>(ax); ay = group_bcast<LPE>(ay);
-      gx = group_bcast<LPE>(gx); gy = group_bcast<LPE>(gy);
-    } else if (!FIXED && lead) {
+    } else if (!FIXED) {
       const int slot = atomicAdd(&s_nreset, 1);   // LDS atomic: compact the block's resets
-      s_slot_of[el] = (int16_t)slot;
-      if (slot < RCAP) { s_reset_el[slot] = (int16_t)el; s_reset_ep[slot] = episode + 1u; }
+      s_slot_of[tid] = (int16_t)slot;
+      if (slot < RCAP) { s_reset_el[slot] = (int16_t)tid; s_reset_ep[slot] = episode + 1u; }
     }
   } else if (valid && MODE != MODE_STEP) {
-    // observe / reset of an unmasked env: near list of the current state, split over the group
+    // observe / reset of an unmasked env: near list of the current state
     const Win g(p, ax, ay);
-    for (int k = q; k < Ns; k += LPE) {
+    for (int k = 0; k < Ns; ++k) {
       const int32_t o = (p.static_obs + (size_t)k * N)[i];
       int f, e;
       if (g.near(px(o), py(o), f, e)) nl.push(f, e);
     }
-    for (int k = q; k < Nd; k += LPE) {
+    for (int k = 0; k < Nd; ++k) {
       const int32_t o = (p.dyn_obs + (size_t)k * N)[i];
       int f, e;
       if (g.near(px(o), py(o), f, e)) nl.push(f, e);
@@ -1619,7 +1500,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void be_kernel(KParams p) {
       wave_resets<WT, NSC, NDC, 64>(p, t, m, i, gid, episode, ax, ay, gx, gy, nl.cnt, xrows, &s_rows[(tid >> 6) * 16][0],
                                     osink, esink);
   }
-  if (POOL && p.stats && !DBG(DBG_NO_STATS)) wave_stats2(done && lead, fin_ret, fin_len, ws, ws_hi);   // (converged)
+  if (POOL && p.stats && !DBG(DBG_NO_STATS)) wave_stats2(done, fin_ret, fin_len, ws, ws_hi);   // (converged)
   DIAG(3);
 
   // ---- observation (prep_state4)
@@ -1634,7 +1515,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void be_kernel(KParams p) {
       if (DBG(DBG_NO_RASTER)) nl.cnt = 0;
       raster_fixed<WT, FIXED>(nl, g, p.R, rows, t_blk[FIXED ? (tid >> 6) : 0]);
 #pragma unroll
-      for (int k = 0; k < Geo<WT>::K; ++k) rows[k] = group_or<LPE>(rows[k] | xrows[k]);
+      for (int k = 0; k < Geo<WT>::K; ++k) rows[k] |= xrows[k];
       flatten<WT>(rows, flat);
       quad = quadrant(ax, ay, gx, gy);
     }
@@ -1642,37 +1523,31 @@ __global__ __launch_bounds__(BLOCK_THREADS) void be_kernel(KParams p) {
       if (valid && flat[0] == 0x12345u && quad == 7) p.obs[i] = 1;   // keep the rows live
       return;
     }
-    if (valid) {  // lane q writes words (bytes, when F % 4 != 0) q, q+LPE, ... of its env's row
+    if (valid) {  // the env's row into the stage: 8-byte words, 4-byte words or bytes, by F's alignment
       auto word = [&](int w) -> uint32_t {
         const int jc = 4 * (w - 1);  // first cell of this word (nibble aligned)
         return w == 0 ? 1u << (8 * quad) : (((flat[jc >> 5] >> (jc & 31)) & 0xFu) * 0x00204081u) & 0x01010101u;
       };
-      if constexpr (LPE == 1 && (F & 7) == 0) {   // 8-byte LDS stores (half the ds_write count)
-        uint2* dst = reinterpret_cast<uint2*>(stage + el * F);
+      if constexpr ((F & 7) == 0) {   // 8-byte LDS stores (half the ds_write count)
+        uint2* dst = reinterpret_cast<uint2*>(stage + tid * F);
 #pragma unroll
         for (int w = 0; w < F / 8; ++w) dst[w] = make_uint2(word(2 * w), word(2 * w + 1));
       } else if constexpr ((F & 3) == 0) {
-        uint32_t* dst = reinterpret_cast<uint32_t*>(stage + el * F);
+        uint32_t* dst = reinterpret_cast<uint32_t*>(stage + tid * F);
 #pragma unroll
-        for (int w0 = 0; w0 < F / 4; w0 += LPE) {
-          const int w = w0 + q;
-          if (w < F / 4) {
-            uint32_t v;
-            if (w == 0) v = 1u << (8 * quad);
-            else {
-              const int jc = 4 * (w - 1);  // first cell of this word (nibble aligned)
-              v = (((flat[jc >> 5] >> (jc & 31)) & 0xFu) * 0x00204081u) & 0x01010101u;
-            }
-            dst[w] = v;
+        for (int w = 0; w < F / 4; ++w) {
+          uint32_t v;
+          if (w == 0) v = 1u << (8 * quad);
+          else {
+            const int jc = 4 * (w - 1);  // first cell of this word (nibble aligned)
+            v = (((flat[jc >> 5] >> (jc & 31)) & 0xFu) * 0x00204081u) & 0x01010101u;
           }
+          dst[w] = v;
         }
       } else {
-        uint8_t* dst = stage + el * F;
+        uint8_t* dst = stage + tid * F;
 #pragma unroll
-        for (int b0 = 0; b0 < F; b0 += LPE) {
-          const int b = b0 + q;
-          if (b < F) dst[b] = (uint8_t)obs_byte<WT>(flat, quad, b);
-        }
+        for (int b = 0; b < F; ++b) dst[b] = (uint8_t)obs_byte<WT>(flat, quad, b);
       }
     }
     DIAG(4);
@@ -1706,9 +1581,9 @@ __global__ __launch_bounds__(BLOCK_THREADS) void be_kernel(KParams p) {
       for (int r0 = 0; r0 < nres; r0 += RCAP) {
         const int nr = min(RCAP, nres - r0);
         if (r0 > 0) {   // more than RCAP resets in this block (e.g. reset of every env): refill the list
-          if (valid && lead && s_slot_of[el] >= r0 && s_slot_of[el] < r0 + RCAP) {
-            const int s = s_slot_of[el] - r0;
-            s_reset_el[s] = (int16_t)el; s_reset_ep[s] = episode + 1u;
+          if (valid && s_slot_of[tid] >= r0 && s_slot_of[tid] < r0 + RCAP) {
+            const int s = s_slot_of[tid] - r0;
+            s_reset_el[s] = (int16_t)tid; s_reset_ep[s] = episode + 1u;
           }
           __syncthreads();
         }
@@ -1798,7 +1673,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void be_kernel(KParams p) {
     const int nvalid = min(EPB, N - blk0);
     copy_out<BLOCK_THREADS>(stage, F, nvalid, (int64_t)blk0, p.obs, p.obs_f32);
   } else {
-    if (valid && lead) {
+    if (valid) {
       const int F = 4 + p.window * p.window;
       const Win g(p, ax, ay);
       write_row_generic<BLOCK_THREADS>(nl, g, quadrant(ax, ay, gx, gy), p.obs ? p.obs + (int64_t)i * F : nullptr,
@@ -1870,20 +1745,23 @@ __device__ __forceinline__ uint32_t pair_or(uint32_t x) {   // OR with the other
   return x | (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0xB1, 0xF, 0xF, false);   // quad_perm 1,0,3,2
 }
 
-// step2_kernel's arguments (launch() fills all three from the one KParams it builds):
-//  * 14 dwords of leading scalars.  gfx950's dispatcher preloads them into user SGPRs while the
-//    wave launches (-amdgpu-kernarg-preload-count, build.py; a by-value struct is not preloaded),
-//    so the loads through them -- the tables, episode / ep_len, every obstacle -- issue at once,
-//    with no scalar load from the kernarg segment in front of them;
-//  * KHot: what the prologue's other loads go through, one 64-byte line of the kernarg segment.
-//    Its scalar load is issued first of all and is the only one the prologue waits for;
-//  * KParams, as every other kernel takes it: read after the prologue's loads are in flight.
-// (Stamps and A/B: DESIGN 3.3, profiles/r08_*.)
-struct alignas(64) KHot {
-  int32_t* agent; int32_t* goal; double* prev_dist; double* total_dist; double* ep_return;
-  const uint8_t* actions; double* stats; int32_t prev_read, goal_change;
+// The finishing path, as measured (us per launch at 65 536 / 32 768 envs, against 5.66-5.69 /
+// 4.59-4.60 before the split: profiles/r07_step2_finish_path_ab.txt); the losing arms are gone:
+//   the pool entry loads  kept: every lane loads its own env's entry, no branch, not waited for;
+//                         lost: only the finishing lanes, in their branch, waited in place (5.73-5.89 / 4.85-5.00)
+//   the statistics fold   kept: after the copy-out, off the path to the wave's last obs store (5.39-5.42 / 4.51);
+//                         lost: before the raster (5.49-5.52 / 4.68-4.69), and between the raster and
+//                         the entry wait (5.64-5.67 / 4.81-4.82)
+// step2_kernel's dynamic LDS, the one source of its offsets and of the launch's byte count:
+//   [near lists: SLOTS x S2_CT lanes x 4 B][obs stage: S2_CT / 2 envs x F bytes]
+// SLOTS: a lane's static and dynamic obstacle slots + 1 (the pushes write one slot ahead)
+template <int WT, int NSC, int NDC>
+struct Step2Lds {
+  static constexpr int SLOTS = (NSC + 1) / 2 + (NDC + 1) / 2 + 1;
+  static constexpr size_t stage = (size_t)SLOTS * S2_CT * 4;
+  static constexpr int bytes = SLOTS * S2_CT * 4 + (S2_CT / 2) * Geo<WT>::F;
 };
-static_assert(sizeof(KHot) == 64, "one line of the kernarg segment");
+static_assert(S2_CT != 256 || Step2Lds<10, 13, 5>::bytes == 24576, "the default shape's LDS");
 template <int WT, int NSC, int NDC, bool POOL = false>
 __global__ __launch_bounds__(S2_CT, 2) void step2_kernel(const Tables* a_tables, uint32_t* a_episode, int32_t* a_ep_len,
                                                          int32_t* a_dyn_obs, uint8_t* a_dyn_goal, int32_t* a_static_obs,
@@ -1909,7 +1787,8 @@ __global__ __launch_bounds__(S2_CT, 2) void step2_kernel(const Tables* a_tables,
   const int N = a_n, tid = (int)threadIdx.x, w = tid >> 6, lane = tid & 63, h = lane & 1;
   DIAG_SARG(0, N);
   const int blk0 = (int)blockIdx.x * EPB, i = blk0 + (tid >> 1), e0 = blk0 + w * EPW;
-  uint8_t* stage_blk = smem + (size_t)(SS + SD + 1) * CT * 4;   // [EPB envs][F]
+  static_assert(SS + SD + 1 == Step2Lds<WT, NSC, NDC>::SLOTS, "the near lists' slots");
+  uint8_t* stage_blk = smem + Step2Lds<WT, NSC, NDC>::stage;   // [EPB envs][F]
   const bool valid = i < N;
   const uint32_t ic = (uint32_t)min(i, N - 1), gid = (uint32_t)a_gid0 + (uint32_t)i;
   NearList<CT> nl{reinterpret_cast<uint32_t*>(smem) + tid, 0};
@@ -1991,7 +1870,7 @@ __global__ __launch_bounds__(S2_CT, 2) void step2_kernel(const Tables* a_tables,
   }
 
   // ---- this lane's dynamic obstacles: draws and moves first (no action needed; ballenv_env.py:323-353)
-  int counter = (int)((double)len0 * p.inv_g1);   // counter == ep_len mod (G+1)
+  int counter = (int)((double)len0 * p.inv_g1);   // counter == ep_len mod (G+1)   // (inline: goal_counter() here moves this kernel's code)
   counter = len0 - counter * (hot.goal_change + 1);
   if (counter < 0) counter += hot.goal_change + 1;
   if (counter > hot.goal_change) counter -= hot.goal_change + 1;
@@ -2015,7 +1894,7 @@ __global__ __launch_bounds__(S2_CT, 2) void step2_kernel(const Tables* a_tables,
   }
   DIAG(11);
   // ---- action -> agent move + clamp (ballenv_env.py:247-259); unit moves and speeds
-  st_flags |= a >= p.num_actions ? (uint32_t)BE_STATUS_BAD_ACTION : 0u;
+  st_flags |= a >= p.num_actions ? (uint32_t)BE_STATUS_BAD_ACTION : 0u;   // (inline: unit_move() here moves this kernel's code)
   const uint32_t sh = 2u * (uint32_t)(a < p.num_actions ? a : 0);
   int ax = min(max(px(agent0) + (int)((p.amx >> sh) & 3u) - 1, 0), p.screen_w);
   int ay = min(max(py(agent0) + (int)((p.amy >> sh) & 3u) - 1, 0), p.screen_h);
@@ -2065,7 +1944,7 @@ __global__ __launch_bounds__(S2_CT, 2) void step2_kernel(const Tables* a_tables,
 
   // ---- distance, reward, done (ballenv_env.py:268-286, 200-229), on both lanes
   double reward = rbase;
-  if (hs) reward -= p.static_penalty;          // statics come first in obstacle_list (Q3)
+  if (hs) reward -= p.static_penalty;          // statics come first in obstacle_list (Q3)   // (inline: collision_penalty() here moves this kernel's code)
   else if (hd) reward -= p.dynamic_penalty;
   ret += reward;
   const int len = len0 + 1;
@@ -2138,22 +2017,11 @@ __global__ __launch_bounds__(S2_CT, 2) void step2_kernel(const Tables* a_tables,
     uint2 q_tv = make_uint2(0u, 0u);
     uint4 qb[7];
     if constexpr (FIN && POOL) {
-#if BE_S2_FIN_LOAD == 1
       const uint32_t x = ((episode + 1u) & 1u) * (uint32_t)N + ic;
       q_tv = pool_ld<uint2>(ptr.pool, x * 8u);
       const uint32_t bo = pool_body((uint32_t)N, x, 28);
 #pragma unroll
       for (int j = 0; j < 7; ++j) qb[j] = pool_ld<uint4>(ptr.pool, bo, 16u * j);
-#else
-      if (do_reset) {   // only the finishing lanes load, and wait here: no pending load past the branch
-        const uint32_t x = ((episode + 1u) & 1u) * (uint32_t)N + (uint32_t)i;
-        q_tv = pool_ld<uint2>(ptr.pool, x * 8u);
-        const uint32_t bo = pool_body((uint32_t)N, x, 28);
-#pragma unroll
-        for (int j = 0; j < 7; ++j) qb[j] = pool_ld<uint4>(ptr.pool, bo, 16u * j);
-        __builtin_amdgcn_s_waitcnt(0);
-      }
-#endif
     }
     if (valid) {   // both lanes of the pair store the env's scalars (the same value to the same address:
                    // one full-wave store per array, no per-lane pointer selects or exec masking)
@@ -2203,7 +2071,7 @@ __global__ __launch_bounds__(S2_CT, 2) void step2_kernel(const Tables* a_tables,
     } else {
       // ---- the finishing path.  The episode statistics fold needs only done, ret and len (even
       // lanes: env order; a reset leaves them alone), so it can run anywhere: after the obs stores
-      // are issued measured fastest (BE_S2_FIN_ORDER) -- the ballot loop's readlanes and the f64
+      // are issued measured fastest (the note above the kernel) -- the ballot loop's readlanes and the f64
       // adds are then behind the wave's last obs store instead of in front of the entry wait
       auto fold = [&]() __attribute__((always_inline)) {
         if (slot && !DBG(DBG_NO_STATS)) {
@@ -2215,9 +2083,6 @@ __global__ __launch_bounds__(S2_CT, 2) void step2_kernel(const Tables* a_tables,
           }
         }
       };
-#if BE_S2_FIN_ORDER == 1
-      fold();
-#endif
       // ONE raster of every lane's own near list: the obs rows of the lanes that do not reset, and,
       // OR-ed over the pair and flattened, the terminal obs of the ones that do (its byte stores wait
       // until the entries have landed)
@@ -2233,9 +2098,6 @@ __global__ __launch_bounds__(S2_CT, 2) void step2_kernel(const Tables* a_tables,
         for (int k = 0; k < KR; ++k) rows[k] = pair_or(xrows[k]);
         flatten<WT>(rows, tflat);
       }
-#if BE_S2_FIN_ORDER == 2
-      fold();
-#endif
       // ---- episode boundary.  A pool entry for the new episode (e + 1) that was written and is still
       // current: copy it (the first use of the loaded values: the wave waits for its entries here)
       bool hit = false;
@@ -2247,11 +2109,9 @@ __global__ __launch_bounds__(S2_CT, 2) void step2_kernel(const Tables* a_tables,
         // asm statements: they emit no instruction and only make the values used here; a plain C++
         // use that the results do not need is removed by the optimiser.  The cost is that a
         // finishing wave with no resetting env (autoreset off) waits for its entries as well
-#if BE_S2_FIN_LOAD == 1
         asm volatile("" :: "v"(q_tv.x), "v"(q_tv.y));
 #pragma unroll
         for (int j = 0; j < 7; ++j) asm volatile("" :: "v"(qb[j].x), "v"(qb[j].y), "v"(qb[j].z), "v"(qb[j].w));
-#endif
         hit = do_reset && q_tv.x == episode + 1u && (q_tv.y & POOL_VALID) != 0u;
 #ifdef BE_DIAG_STAMPS
         if (__ballot(do_reset)) DIAG(9);   // (stamps build: this wave's entries landed)
@@ -2324,9 +2184,7 @@ __global__ __launch_bounds__(S2_CT, 2) void step2_kernel(const Tables* a_tables,
       DIAG(3);
       if (DBG(DBG_NO_OBS)) return;
       obs_out(xrows);   // a reset env's new rows, the other lanes' rows of the raster above
-#if BE_S2_FIN_ORDER == 3
       fold();
-#endif
       DIAG(6);
     }
   };
@@ -2355,6 +2213,15 @@ __global__ __launch_bounds__(S2_CT, 2) void step2_kernel(const Tables* a_tables,
 //    wave's obs stores: 4.01 against 4.03 us with the barrier right after the physics,
 //    profiles/r04_stepw_late_fold_ab.txt) wave 0 folds them in env order -- the same sums, in
 //    the same order, as the one-lane kernel.
+// Where stepw_kernel loads the pool entries of its finished envs (step2_kernel loads them at the head
+// of its finishing path, which only the waves with a finished env run): right after done is known,
+// before the physics stores, waited for inside that (divergent) branch -- only the waves with a
+// finished env wait.
+// (Measured and dropped, profiles/r06_pool_ab.txt: the loads inside the reset section, the uniform
+// `if (m)` of the waves with a finished env, after the stores; the loads unwaited in the branch --
+// the waitcnt pass then drains every outstanding store at the merge before the reset loop, in
+// every wave; branch-free buffer loads with an out-of-range offset for the lanes without a
+// finished env; the loads after the stores outside the reset section.)
 template <int L>
 __device__ __forceinline__ uint32_t lane_group_or(uint32_t x) {   // OR over the aligned group of L lanes
   static_assert(L == 4 || L == 8, "L must be 4 or 8");
@@ -2448,11 +2315,7 @@ __global__ __launch_bounds__(32 * L) void stepw_kernel(KParams p) {
   PH(0);
 
   // ---- this lane's dynamic obstacles (ballenv_env.py:323-353): draws and moves need no action
-  int counter = (int)((double)len0 * p.inv_g1);   // counter == ep_len mod (G+1)
-  counter = len0 - counter * (p.goal_change + 1);
-  if (counter < 0) counter += p.goal_change + 1;
-  if (counter > p.goal_change) counter -= p.goal_change + 1;
-  const bool change = counter >= p.goal_change;
+  const bool change = goal_counter(len0, p.goal_change, p.inv_g1) >= p.goal_change;
   const u4 b0 = DBG(DBG_NO_PHILOX) ? u4{gid, episode, 7u, 9u} : philox(gid, episode, (uint32_t)len0, tag(PURPOSE_STEP_OBS, 0u), p.seed);
   uint32_t st_flags = 0u;
   int ngs[SD];
@@ -2468,7 +2331,7 @@ __global__ __launch_bounds__(32 * L) void stepw_kernel(KParams p) {
   }
   PH(1);
   // ---- action -> agent move + clamp (ballenv_env.py:247-259); unit moves and speeds
-  st_flags |= a >= p.num_actions ? (uint32_t)BE_STATUS_BAD_ACTION : 0u;
+  st_flags |= a >= p.num_actions ? (uint32_t)BE_STATUS_BAD_ACTION : 0u;   // (inline: unit_move() here moves this kernel's code)
   const uint32_t sh = 2u * (uint32_t)(a < p.num_actions ? a : 0);
   int ax = min(max(px(agent0) + (int)((p.amx >> sh) & 3u) - 1, 0), p.screen_w);
   int ay = min(max(py(agent0) + (int)((p.amy >> sh) & 3u) - 1, 0), p.screen_h);
@@ -2507,9 +2370,7 @@ __global__ __launch_bounds__(32 * L) void stepw_kernel(KParams p) {
   PH(3);
 
   // ---- reward, done (ballenv_env.py:268-286, 200-229), on every lane of the group
-  double reward = rbase;
-  if (hs) reward -= p.static_penalty;          // statics come first in obstacle_list (Q3)
-  else if (hd) reward -= p.dynamic_penalty;
+  const double reward = collision_penalty(rbase, hs, hd, p.static_penalty, p.dynamic_penalty);
   ret += reward;
   const int len = len0 + 1;
   const bool env_done = (dist < p.threshold_goal) || hs || hd;
@@ -2526,7 +2387,6 @@ __global__ __launch_bounds__(32 * L) void stepw_kernel(KParams p) {
   uint4 q0, q1;
   uint2 q2;
   uint32_t q_dp[SD], q_so[SS];
-#if BE_POOL_MODE == 1
   if constexpr (POOL) if (ptry) {
     const uint32_t x = ((episode + 1u) & 1u) * (uint32_t)N + (uint32_t)i;
     q_tv = pool_ld<uint2>(p.pool, x * 8u);
@@ -2540,7 +2400,6 @@ __global__ __launch_bounds__(32 * L) void stepw_kernel(KParams p) {
     for (int j = 0; j < SS; ++j) q_so[j] = pool_ld<uint32_t>(p.pool, bo + 4u * (uint32_t)min(L * j + h, NSC - 1), 4u * PB_OBS);
     __builtin_amdgcn_s_waitcnt(0);   // here, in the branch: no pending pool load past its end
   }
-#endif
   if (valid) {   // the per-env scalars: one full-wave store per array
     const uint32_t iu = (uint32_t)i;   // every lane of the group: the same value to the same address
     st_ws(p.reward, iu, reward);
@@ -2588,20 +2447,6 @@ __global__ __launch_bounds__(32 * L) void stepw_kernel(KParams p) {
   // no wave without a finished env waits for the pool loads; every use of a loaded value is inside)
   bool hit = false;
   if (__ballot(ptry)) {
-#if BE_POOL_MODE == 5
-    if (ptry) {
-      const uint32_t x = ((episode + 1u) & 1u) * (uint32_t)N + (uint32_t)i;
-      q_tv = pool_ld<uint2>(p.pool, x * 8u);
-      const uint32_t bo = pool_body((uint32_t)N, x, 28);
-      q0 = pool_ld<uint4>(p.pool, bo, 0u);
-      q1 = pool_ld<uint4>(p.pool, bo, 16u);
-      q2 = pool_ld<uint2>(p.pool, bo, 32u);
-#pragma unroll
-      for (int j = 0; j < SD; ++j) q_dp[j] = pool_ld<uint32_t>(p.pool, bo + 4u * (uint32_t)min(L * j + h, NDC - 1), 4u * (PB_OBS + NSC));
-#pragma unroll
-      for (int j = 0; j < SS; ++j) q_so[j] = pool_ld<uint32_t>(p.pool, bo + 4u * (uint32_t)min(L * j + h, NSC - 1), 4u * PB_OBS);
-    }
-#endif
     hit = ptry && q_tv.x == episode + 1u && (q_tv.y & POOL_VALID) != 0u;
     if (hit) {   // every lane of the group stores the scalars (as the physics did) and its own slots
       const uint32_t iu = (uint32_t)i;
@@ -2887,7 +2732,7 @@ __global__ __launch_bounds__(32 * L) void rolloutw_kernel(KParams p) {
   // the obstacles' goal-change counter (== ep_len mod (G+1)) kept incrementally, and each step's
   // Philox block computed one step ahead: the next step's (episode, ep_len + 1) block runs beside
   // this step's work, off its critical path (recomputed after a reset for the envs that reset)
-  int counter = (int)((double)len * p.inv_g1);
+  int counter = (int)((double)len * p.inv_g1);   // (inline: goal_counter() here moves this kernel's code)
   counter = len - counter * (p.goal_change + 1);
   if (counter < 0) counter += p.goal_change + 1;
   if (counter > p.goal_change) counter -= p.goal_change + 1;
@@ -2914,7 +2759,7 @@ __global__ __launch_bounds__(32 * L) void rolloutw_kernel(KParams p) {
     }
     PH(0);
     // ---- action -> agent move + clamp (ballenv_env.py:247-259)
-    st_flags |= a >= p.num_actions ? (uint32_t)BE_STATUS_BAD_ACTION : 0u;
+    st_flags |= a >= p.num_actions ? (uint32_t)BE_STATUS_BAD_ACTION : 0u;   // (inline: unit_move() here moves this kernel's code)
     const uint32_t sh = 2u * (uint32_t)(a < p.num_actions ? a : 0);
     ax = min(max(ax + (int)((p.amx >> sh) & 3u) - 1, 0), p.screen_w);
     ay = min(max(ay + (int)((p.amy >> sh) & 3u) - 1, 0), p.screen_h);
@@ -2947,9 +2792,7 @@ __global__ __launch_bounds__(32 * L) void rolloutw_kernel(KParams p) {
     uint32_t rows = word & 0xFFFFFu;
     PH(2);
     // ---- reward, done (ballenv_env.py:268-286, 200-229)
-    double reward = rbase;
-    if (hs) reward -= p.static_penalty;          // statics come first in obstacle_list (Q3)
-    else if (hd) reward -= p.dynamic_penalty;
+    const double reward = collision_penalty(rbase, hs, hd, p.static_penalty, p.dynamic_penalty);
     ret += reward;
     ++len;
     const bool env_done = (dist < p.threshold_goal) || hs || hd;
@@ -3122,8 +2965,30 @@ __global__ __launch_bounds__(32 * L) void rolloutw_kernel(KParams p) {
 // same Philox keys as be_policy_act, so the trajectory is bit-identical to the two-launch
 // loop (tests/test_gpu_rollout.py::test_policy_rollout_matches_two_launch_loop).  The obs is
 // written per step only when recorded (p.obs), and the last one to p.obs_last.
+//
+// rollout_kernel's dynamic LDS, the one source of its offsets and of the launch's byte count:
+//   [near lists: G+1 slots x 256 lanes x 4 B][obs stage: 256 envs x F bytes]        (16-byte aligned)
+//   HT > 0: [PolLayout image + scratch][chunk partials: POL_CHUNKS x 4 waves x 16 envs x NO f32]
+//   [row-span table (build_span_table): (W + 2R)(R + 2) x 2 B -- the only part that grows with R]
+// The W = 10 policy rollout sits 72 B under the CU's 160 KB at the default R = 25 (fits_lds, abi.hip).
+template <int WT, int NSC, int NDC, int HT = 0, int KS = 1, int NO = 10>
+struct RolloutLds {
+  static constexpr int G = NSC + NDC, F = Geo<WT>::F;
+  static constexpr int POL_LDS = HT > 0 ? pol_layout(HT > 0 ? HT : 1, KS, NO).lds : 0;
+  static_assert(POL_LDS % 16 == 0, "the policy image keeps what follows it 16-byte aligned");
+  static constexpr size_t stage = (size_t)(G + 1) * BLOCK_THREADS * 4;
+  static constexpr int pol = ((G + 1) * BLOCK_THREADS * 4 + BLOCK_THREADS * F + 15) & ~15;   // the policy image
+  static constexpr int partials = pol + POL_LDS;
+  static constexpr int span = partials + (HT > 0 ? POL_CHUNKS * (BLOCK_THREADS / 64) * 16 * NO * 4 : 0);
+  __host__ __device__ static constexpr int bytes(int R) { return span + (WT + 2 * R) * (R + 2) * 2; }
+};
+static_assert(RolloutLds<10, 13, 5>::bytes(25) == 49320 && RolloutLds<5, 13, 5>::bytes(25) == 29850, "the default shapes' LDS");
+// (with the kernel's 3 952 B of static LDS the W = 10 policy rollout uses 163 768 of 163 840 bytes)
+static_assert(RolloutLds<10, 13, 5, 13, 2, 10>::bytes(25) == 159816 && RolloutLds<5, 13, 5, 8, 1, 10>::bytes(25) == 81530,
+              "the policy rollouts' LDS at the default R = 25");
 template <int WT, int NSC, int NDC, int HT = 0, int KS = 1, int NO = 10>
 __global__ __launch_bounds__(BLOCK_THREADS) void rollout_kernel(KParams p) {
+  using Lds = RolloutLds<WT, NSC, NDC, HT, KS, NO>;
   constexpr int KR = Geo<WT>::K, F = Geo<WT>::F, G = NSC + NDC, NWAVE = BLOCK_THREADS / 64;
   constexpr bool POL = HT > 0;
   constexpr PolLayout PL = pol_layout(HT > 0 ? HT : 1, KS, NO);
@@ -3138,14 +3003,13 @@ __global__ __launch_bounds__(BLOCK_THREADS) void rollout_kernel(KParams p) {
   const int nrows = max(0, min(64, N - e0));     // this wave's valid obs rows
   const uint32_t ic = (uint32_t)min(i, N - 1), gid = (uint32_t)p.gid0 + (uint32_t)i;
   NearList<BLOCK_THREADS> nl{reinterpret_cast<uint32_t*>(smem) + tid, 0};
-  uint8_t* stage_blk = smem + (size_t)(G + 1) * BLOCK_THREADS * 4;   // [256 envs][F]: row = tid
+  uint8_t* stage_blk = smem + Lds::stage;                             // [256 envs][F]: row = tid
   uint8_t* stage = stage_blk + (size_t)w * 64 * F;                    // this wave's 64 rows
   // POL: PolLayout image + scratch, 16-byte aligned (a constant offset from the LDS base keeps the
   // accesses ds_* -- an integer round trip of the pointer would turn them into flat accesses)
-  constexpr int POL_OFF = ((G + 1) * BLOCK_THREADS * 4 + BLOCK_THREADS * F + 15) & ~15;
-  uint8_t* pimg = smem + POL_OFF;
+  uint8_t* pimg = smem + Lds::pol;
   // the row-span table (build_span_table): after the stage, or (POL) after the chunk partials
-  uint16_t* mt = reinterpret_cast<uint16_t*>(POL ? pimg + PL.lds + POL_CHUNKS * NWAVE * 16 * NO * 4 : smem + POL_OFF);
+  uint16_t* mt = reinterpret_cast<uint16_t*>(smem + Lds::span);
 
   // ---- state into registers (straight-line, use order)
   const uint32_t tword = ld_s(reinterpret_cast<const uint32_t*>(p.tables), (uint32_t)min(tid, TW - 1));
@@ -3181,7 +3045,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void rollout_kernel(KParams p) {
     if (tid < 3) reinterpret_cast<int*>(pimg + PL.count)[tid] = 0;
   }
   __syncthreads();   // tables (and the policy image, the obs rows, the list counters) staged
-  float* pbuf_base = reinterpret_cast<float*>(pimg + PL.lds);   // POL: chunk partials of a round of tiles
+  float* pbuf_base = reinterpret_cast<float*>(smem + Lds::partials);   // POL: chunk partials of a round of tiles
   if constexpr (POL) {
     if (valid) {   // what be_policy_act's scan decides from the same bytes
       const uint8_t* row = stage + lane * F;
@@ -3350,19 +3214,14 @@ __global__ __launch_bounds__(BLOCK_THREADS) void rollout_kernel(KParams p) {
     const int gx = px(goal), gy = py(goal);
     PH(4);
     // ---- action -> agent move + clamp (ballenv_env.py:247-259)
-    st_flags |= a >= p.num_actions ? (uint32_t)BE_STATUS_BAD_ACTION : 0u;
-    const uint32_t sh = 2u * (uint32_t)(a < p.num_actions ? a : 0);
-    const int dx = (int)((p.amx >> sh) & 3u) - 1, dy = (int)((p.amy >> sh) & 3u) - 1;
+    int dx, dy;
+    unit_move(a, p.num_actions, p.amx, p.amy, dx, dy, st_flags);
     ax = min(max(ax + dx, 0), p.screen_w);   // unit speeds (pick_rollout's precondition)
     ay = min(max(ay + dy, 0), p.screen_h);
     bool hs = false, hd = false;
     nl.cnt = 0;
-    // ---- dynamic obstacles (counter == ep_len mod (G+1): all start at 0 on reset)
-    int counter = (int)((double)len * p.inv_g1);
-    counter = len - counter * (p.goal_change + 1);
-    if (counter < 0) counter += p.goal_change + 1;
-    if (counter > p.goal_change) counter -= p.goal_change + 1;
-    const bool change = counter >= p.goal_change;
+    // ---- dynamic obstacles
+    const bool change = goal_counter(len, p.goal_change, p.inv_g1) >= p.goal_change;
     const u4 b0 = philox(gid, episode, (uint32_t)len, tag(PURPOSE_STEP_OBS, 0u), p.seed);
     u4 b1{0u, 0u, 0u, 0u};
     if (NDC > 5) b1 = philox(gid, episode, (uint32_t)len, tag(PURPOSE_STEP_OBS, 1u), p.seed);
@@ -3393,8 +3252,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void rollout_kernel(KParams p) {
     const double dist = calc_dist_lib(gx, gy, ax, ay);
     double reward = 0.0 - p.time_penalty;
     reward += (old_dist - dist) / total;
-    if (hs) reward -= p.static_penalty;          // statics come first in obstacle_list (Q3)
-    else if (hd) reward -= p.dynamic_penalty;
+    reward = collision_penalty(reward, hs, hd, p.static_penalty, p.dynamic_penalty);
     ret += reward;
     ++len;
     const bool env_done = (dist < p.threshold_goal) || hs || hd;
@@ -3548,868 +3406,144 @@ __global__ void sample_actions_kernel(uint8_t* out, int32_t n, int32_t steps, in
   }
 }
 
-// ------------------------------------------------------------------ dispatch
-using KFn = void (*)(KParams);
-// step2_kernel: its leading scalar arguments (preloaded into SGPRs), KHot, then the KParams
-using KFn2 = void (*)(const Tables*, uint32_t*, int32_t*, int32_t*, uint8_t*, int32_t*, int32_t, int32_t, KHot, KParams);
+}  // namespace
+
+// ------------------------------------------------------------------ dispatch (step_types.h)
+namespace bestep {
+namespace {
+
 template <int WT>
 KFn kernel_for(int mode) {
   return mode == MODE_STEP ? be_kernel<WT, MODE_STEP>
                            : (mode == MODE_RESET ? be_kernel<WT, MODE_RESET> : be_kernel<WT, MODE_OBSERVE>);
 }
 
-struct Launch { KFn fn; int epb; int lds; char name[48]; int threads = BLOCK_THREADS; KFn2 fn2 = nullptr; };   // fn2: step2_kernel (fn is nullptr then)
-
-// Fixed-shape step kernels for the reference's default obstacle counts (ball_cnn_ac3.py:40-41).
-constexpr int FIX_NS = 13, FIX_ND = 5;   // the reference's obstacle counts (ball_cnn_ac3.py:40-41)
-// The fixed-shape kernels address per-env arrays as a uniform base + a 32-bit byte offset (ld_s /
-// st_ws): element i of an 8-byte array needs i < 2^29.  Larger batches (~150 GB of state and outputs)
-// take the generic kernels, which index in 64 bits.
-constexpr int64_t FIX_MAX_ENVS = 1ll << 29;
-
-// pool: the variant that copies finished envs' resets from the autoreset pool (step2_kernel /
-// stepw_kernel<..., true>; the context passes it only with a pool allocated)
-Launch pick_kernel(const be_config& c, int mode, bool fixed_ok = false, int lanes10 = 1, int lpe5 = 0, bool pool = false) {
-  int W = c.window;
-  const int F = 4 + W * W, nobs = c.num_static + c.num_dynamic;
-  Launch L{nullptr, 0, 0, {0}};
-  bool staged = true;
-  const bool fixed = fixed_ok && mode == MODE_STEP && c.num_static == FIX_NS && c.num_dynamic == FIX_ND &&
-                     c.speed_x == 1 && c.speed_y == 1 && c.radius_obstacle + c.radius_agent <= HW_MAX &&
-                     (int64_t)c.num_envs < FIX_MAX_ENVS;
-  if (fixed && lanes10 == 2 && W == 10 && span_fits(W, c.radius_obstacle + c.radius_agent) &&
-      (int64_t)c.num_envs * FIX_NS < (1ll << 30)) {
-    // two lanes per env (step2_kernel): 32 envs per wave, 128 per block
-    L.fn2 = pool ? step2_kernel<10, FIX_NS, FIX_ND, true> : step2_kernel<10, FIX_NS, FIX_ND, false>;
-    L.epb = S2_CT / 2;
-    L.threads = S2_CT;
-    constexpr int SLOTS = (FIX_NS + 1) / 2 + (FIX_ND + 1) / 2 + 1;
-    L.lds = SLOTS * S2_CT * 4 + L.epb * F;
-    snprintf(L.name, sizeof L.name, "step2_kernel<10, %d, %d, %s>", FIX_NS, FIX_ND, pool ? "true" : "false");
-    return L;
-  }
-  if (fixed && W == 5 && (lpe5 == 4 || lpe5 == 8) && (int64_t)c.num_envs * FIX_NS < (1ll << 30)) {
-    // L lanes per env (stepw_kernel): 32 envs per block (its reset sink stores obstacles at 32-bit
-    // byte offsets, as step2_kernel's does: NS*N < 2^30)
-    L.fn = lpe5 == 8 ? (pool ? stepw_kernel<5, FIX_NS, FIX_ND, 8, true> : stepw_kernel<5, FIX_NS, FIX_ND, 8, false>)
-                     : (pool ? stepw_kernel<5, FIX_NS, FIX_ND, 4, true> : stepw_kernel<5, FIX_NS, FIX_ND, 4, false>);
-    L.epb = 32;
-    L.threads = 32 * lpe5;
-    L.lds = 0;
-    snprintf(L.name, sizeof L.name, "stepw_kernel<5, %d, %d, %d, %s>", FIX_NS, FIX_ND, lpe5, pool ? "true" : "false");
-    return L;
-  }
-  if (fixed && W == 10) {
-    L.fn = pool ? be_kernel<10, MODE_STEP, FIX_NS, FIX_ND, true> : be_kernel<10, MODE_STEP, FIX_NS, FIX_ND, false>;
-    L.epb = BLOCK_THREADS; W = -1;
-  } else if (fixed && W == 5) {
-    L.fn = pool ? be_kernel<5, MODE_STEP, FIX_NS, FIX_ND, true> : be_kernel<5, MODE_STEP, FIX_NS, FIX_ND, false>;
-    L.epb = BLOCK_THREADS; W = -1;
-  }
-  switch (W) {
-    case -1: break;
-#define BE_CASE(n) case n: L.fn = kernel_for<n>(mode); L.epb = envs_per_block(n); break;
-    BE_CASE(1) BE_CASE(2) BE_CASE(3) BE_CASE(4) BE_CASE(5) BE_CASE(6) BE_CASE(7) BE_CASE(8)
-    BE_CASE(9) BE_CASE(10) BE_CASE(11) BE_CASE(12) BE_CASE(13) BE_CASE(14) BE_CASE(15) BE_CASE(16)
-    BE_CASE(21)
-#undef BE_CASE
-    default: L.fn = kernel_for<0>(mode); L.epb = envs_per_block(0); staged = false; break;
-  }
-  if (L.fn) {
-    if (W == -1) snprintf(L.name, sizeof L.name, "be_kernel<%d, %d, %d, %d, %s>", c.window, mode, FIX_NS, FIX_ND, pool ? "true" : "false");
-    else snprintf(L.name, sizeof L.name, "be_kernel<%d, %d, 0, 0, false>", staged ? W : 0, mode);
-  }
-  const int near_bytes = (nobs + 1) * BLOCK_THREADS * 4;   // +1: predicated pushes write one slot ahead
-  const int stage_bytes = staged ? L.epb * F : 0;
-  L.lds = (near_bytes + stage_bytes + 15) & ~15;
-  if (L.lds == 0) L.lds = 16;
-  return L;
-}
-
-// The fused rollout kernel for the same fixed shapes (nullptr: not applicable).
-Launch pick_rollout(const be_config& c, bool fixed_ok, int lpe5 = 0) {
-  Launch L{nullptr, BLOCK_THREADS, 0, {0}};
-  const bool fixed = fixed_ok && c.num_static == FIX_NS && c.num_dynamic == FIX_ND && c.speed_x == 1 &&
-                     c.speed_y == 1 && c.radius_obstacle + c.radius_agent <= HW_MAX && (int64_t)c.num_envs < FIX_MAX_ENVS;
-  if (fixed && c.window == 5 && (lpe5 == 4 || lpe5 == 8)) {   // small batches: L lanes per env, 32-env blocks
-    L.fn = lpe5 == 8 ? rolloutw_kernel<5, FIX_NS, FIX_ND, 8> : rolloutw_kernel<5, FIX_NS, FIX_ND, 4>;
-    L.epb = 32;
-    L.threads = 32 * lpe5;
-    L.lds = 0;
-    snprintf(L.name, sizeof L.name, "rolloutw_kernel<5, %d, %d, %d>", FIX_NS, FIX_ND, lpe5);
-    return L;
-  }
-  if (fixed && c.window == 10) L.fn = rollout_kernel<10, FIX_NS, FIX_ND>;
-  else if (fixed && c.window == 5) L.fn = rollout_kernel<5, FIX_NS, FIX_ND>;
-  L.lds = ((FIX_NS + FIX_ND + 1) * BLOCK_THREADS * 4 + BLOCK_THREADS * (4 + c.window * c.window) + 15) & ~15;
-  const int R = c.radius_obstacle + c.radius_agent;
-  L.lds += (c.window + 2 * R) * (R + 2) * 2;   // the row-span table
-  if (L.fn) snprintf(L.name, sizeof L.name, "rollout_kernel<%d, %d, %d, 0, 1, 10>", c.window, FIX_NS, FIX_ND);
-  return L;
-}
-
-// The fused policy rollout kernel: fixed env shape and the select_action kernel's Policy(W)
-// shapes (H 208 / W 10 and H 128 / W 5, 9 actions).
-Launch pick_policy_rollout(const be_config& c, bool fixed_ok, int HT, int KS, int NO) {
-  Launch L{nullptr, BLOCK_THREADS, 0, {0}};
-  const bool fixed = fixed_ok && c.num_static == FIX_NS && c.num_dynamic == FIX_ND && c.speed_x == 1 &&
-                     c.speed_y == 1 && c.radius_obstacle + c.radius_agent <= HW_MAX && (int64_t)c.num_envs < FIX_MAX_ENVS;
-  if (fixed && c.window == 10 && HT == 13 && KS == 2 && NO == 10)
-    L.fn = rollout_kernel<10, FIX_NS, FIX_ND, 13, 2, 10>;
-  else if (fixed && c.window == 5 && HT == 8 && KS == 1 && NO == 10)
-    L.fn = rollout_kernel<5, FIX_NS, FIX_ND, 8, 1, 10>;
-  const PolLayout PL = pol_layout(HT, KS, NO);
-  L.lds = (FIX_NS + FIX_ND + 1) * BLOCK_THREADS * 4 + BLOCK_THREADS * (4 + c.window * c.window);
-  L.lds = ((L.lds + 15) & ~15) + PL.lds;
-  L.lds = ((L.lds + 15) & ~15) + POL_CHUNKS * (BLOCK_THREADS / 64) * 16 * NO * 4;   // chunk partials
-  const int R = c.radius_obstacle + c.radius_agent;
-  L.lds += (c.window + 2 * R) * (R + 2) * 2;   // the row-span table (3.2 KB at W = 10, R = 25: fits the CU's 160 KB)
-  return L;
+// The config's part of the fixed-shape preconditions: the reference's obstacle counts, unit agent
+// speeds (the window's cell step), a half-width table for R, 32-bit byte offsets into 8-byte arrays.
+bool fixed_shape(const be_config& c, bool fixed_ok) {
+  return fixed_ok && c.num_static == FIX_NS && c.num_dynamic == FIX_ND && c.speed_x == 1 && c.speed_y == 1 &&
+         c.radius_obstacle + c.radius_agent <= HW_MAX && (int64_t)c.num_envs < FIX_MAX_ENVS;
 }
 
 }  // namespace
 
-// ====================================================================== C ABI
-struct be_ctx {
-  be_config cfg;
-  TablesX tables;
-  KParams base;      // config-derived part of every launch's KParams
-  int device;
-  int* status;
-  TablesX* d_tables;
-  bool generic_only;   // BALLENV_GENERIC_KERNELS=1: never use the fixed-shape step kernels (A/B diagnostics)
-  bool unit_moves;     // every action move in {-1,0,1}^2 (fixed-shape kernels' packed table)
-  bool distinct_goals; // >= 2 pairwise-distinct goals (fixed-shape kernels' arithmetic newGoalList)
-  int step_lanes;      // W = 10: lanes per env of the fixed step kernel (1: be_kernel; 2: step2_kernel)
-  int step5_lpe;       // W = 5: lanes per env of the fixed step kernel (1: be_kernel; 4 / 8: stepw_kernel)
-  int roll5_lpe;       // W = 5: lanes per env of the fused rollout (1: rollout_kernel; 4 / 8: rolloutw_kernel)
-  int max_lds;         // the device's LDS bytes per workgroup
-  Launch step_launch[2];   // be_step's kernel without / with the fixed-shape preconditions (fixed per context)
-  Launch step_launch_pool; // the fixed-shape kernel's pool variant (when the context has a pool)
-  int64_t blob_hdr[8]; // be_save_state's header (host memory that outlives the async copy)
-  // the autoreset pool (layout at pool_body): allocated when be_step's fixed-shape kernel consumes it
-  uint32_t* pool;      // nullptr: no pool (every reset inline)
-  int64_t pool_bytes;
-  KFn pool_fill;       // pool_fill_kernel<W, 13, 5>
-  int pool_period;     // be_step queues a fill every pool_period step launches (0: only be_reset / be_load_state / be_pool_fill)
-  int pool_calls;      // step launches since the last fill
-  const void* pool_owner;   // the state (its episode array) the pool serves: other states step without it
-  mutable struct { KFn fn; int lds; bool ok; } lds_cache[4];   // fits_lds() answers per (kernel, dynamic LDS)
-  mutable std::mutex lds_mu;                                    // guards lds_cache (const entries may race)
-  char err[512];
-};
-
-// Does a fused kernel's LDS (static + this launch's dynamic bytes) fit one workgroup?  The fused
-// rollouts' dynamic LDS grows with R = radius_obstacle + radius_agent (near lists, row-span
-// table) and the config-5 kernel is within 72 B of the CU's 160 KB at the default R = 25, so a
-// larger R must take the per-step fallback instead of failing the launch.
-static bool fits_lds(const be_ctx* ctx, const Launch& L) {
-  if (!L.fn) return false;
-  std::lock_guard<std::mutex> lock(ctx->lds_mu);
-  for (auto& c : ctx->lds_cache)
-    if (c.fn == L.fn && c.lds == L.lds) return c.ok;
-  hipFuncAttributes fa;
-  bool ok = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(L.fn)) == hipSuccess &&
-            (int64_t)fa.sharedSizeBytes + L.lds <= (int64_t)ctx->max_lds;
-  for (auto& c : ctx->lds_cache)
-    if (!c.fn) { c.fn = L.fn; c.lds = L.lds; c.ok = ok; break; }
-  return ok;
-}
-
-static thread_local char g_err[512];
-
-static int fail(be_ctx* ctx, int code, const char* fmt, const char* detail) {
-  char* dst = ctx ? ctx->err : g_err;
-  snprintf(dst, 512, fmt, detail ? detail : "");
-  return code;
-}
-
-#define HIP_TRY(ctx, expr)                                                                     \
-  do {                                                                                         \
-    hipError_t e_ = (expr);                                                                    \
-    if (e_ != hipSuccess) return fail(ctx, BE_E_HIP, "HIP error: %s", hipGetErrorString(e_)); \
-  } while (0)
-
-// library-internal accessors for the other translation units (csrc/internal.h)
-be_ctx_view be_ctx_get(const be_ctx* ctx) {
-  be_ctx_view v;
-  v.num_envs = ctx->cfg.num_envs; v.window = ctx->cfg.window; v.device = ctx->device;
-  v.num_static = ctx->cfg.num_static; v.num_dynamic = ctx->cfg.num_dynamic;
-  v.env_offset = ctx->cfg.env_offset;
-  return v;
-}
-int be_ctx_fail(be_ctx* ctx, int code, const char* msg) { return fail(ctx, code, "%s", msg); }
-static int check_state(be_ctx* ctx, const be_state* st);
-int be_ctx_check_state(be_ctx* ctx, const be_state* st) { return check_state(ctx, st); }
-
-extern "C" {
-
-int be_abi_version(void) { return BE_ABI_VERSION; }
-
-BE_DIAG_STEP_ENTRIES   // diagnostics builds only (diag.h)
-
-int be_config_default(be_config* c, int32_t num_envs, int32_t window) {
-  if (!c) return fail(nullptr, BE_E_INVALID, "%s", "cfg is NULL");
-  memset(c, 0, sizeof(*c));
-  c->num_envs = num_envs; c->window = window; c->env_offset = 0; c->seed = 0xBA11ull;
-  c->screen_width = 500; c->screen_height = 500;                                     // ballenv_env.py:11-18
-  c->strip_obs_x = 0; c->strip_obs_y = 20; c->strip_goal_x = 500; c->strip_goal_y = 20;
-  c->strip_agent_x = 500; c->strip_agent_y = 10;
-  c->radius_obstacle = 20; c->radius_agent = 5; c->speed_x = 1; c->speed_y = 1;     // :49-54
-  c->threshold_goal = 10.0; c->time_penalty = 0.0; c->min_spawn_dist = 50.0;        // :64-65, :122
-  c->num_static = 13; c->num_dynamic = 5; c->static_penalty = 1.0; c->dynamic_penalty = 8000.0;  // ball_cnn_ac3.py:40-51
-  c->goal_change_step = 50; c->obs_certainty = 60;
-  static const int goals[5][2] = {{12, 122}, {123, 93}, {87, 150}, {430, 440}, {230, 11}};
-  c->num_goals = 5;
-  for (int g = 0; g < 5; ++g) { c->goals[g][0] = goals[g][0]; c->goals[g][1] = goals[g][1]; }
-  for (int k = 0; k < 5; ++k) c->obstacle_speed[k] = 1;
-  static const int moves[9][2] = {{1, 1}, {1, -1}, {1, 0}, {0, 1}, {0, -1}, {0, 0}, {-1, 1}, {-1, 0}, {-1, -1}};
-  c->num_actions = 9;                                                                // ball_cnn_ac3.py:530
-  for (int a = 0; a < 9; ++a) { c->actions[a][0] = moves[a][0]; c->actions[a][1] = moves[a][1]; }
-  c->time_limit = 1000; c->autoreset = 1;                                            // gym_ballenv/__init__.py:7
-  return BE_OK;
-}
-
-int be_config_check(const be_config* c, char* msg, int32_t msg_len) {
-  char buf[256] = {0};
-#define BE_REQ(cond, text) do { if (!(cond)) { snprintf(buf, sizeof buf, "%s", text); goto bad; } } while (0)
-  BE_REQ(c != nullptr, "cfg is NULL");
-  BE_REQ(c->num_envs >= 1, "num_envs must be >= 1");
-  BE_REQ(c->window >= 1 && c->window <= BE_MAX_WINDOW, "window must be in [1, 64]");
-  BE_REQ(c->num_static >= 0 && c->num_static <= BE_MAX_STATIC, "num_static must be in [0, 64]");
-  BE_REQ(c->num_dynamic >= 0 && c->num_dynamic <= BE_MAX_DYNAMIC, "num_dynamic must be in [0, 32]");
-  BE_REQ(c->env_offset >= 0 && c->env_offset + (int64_t)c->num_envs <= (1ll << 32), "global env ids must fit in 32 bits");
-  BE_REQ(c->screen_width >= 1 && c->screen_width <= 16384 && c->screen_height >= 1 && c->screen_height <= 16384,
-         "screen size must be in [1, 16384]");
-  BE_REQ(c->strip_goal_x >= 1 && c->strip_goal_x <= c->screen_width + 16384 && c->strip_goal_y >= 1 &&
-         c->strip_goal_y <= c->screen_height + 16384, "goal strips must give non-empty randint ranges");
-  BE_REQ(c->strip_agent_x >= 1 && c->strip_agent_x <= 16384 && c->strip_agent_y >= 1 && c->strip_agent_y <= 16384,
-         "agent strips must give non-empty randint ranges");
-  BE_REQ(c->screen_width - 2 * c->strip_obs_x >= 1 && c->screen_height - 2 * c->strip_obs_y >= 1,
-         "obstacle strips must give non-empty randint ranges");
-  BE_REQ(c->radius_obstacle >= 0 && c->radius_agent >= 0 && c->radius_obstacle + c->radius_agent <= 2047,
-         "radii must be >= 0 with r_obstacle + r_agent <= 2047");
-  BE_REQ(c->speed_x >= 1 && c->speed_y >= 1 && c->speed_x <= 1024 && c->speed_y <= 1024,
-         "agent speeds (window cell steps) must be in [1, 1024]");
-  BE_REQ(c->speed_x * (c->window / 2) <= 16384 && c->speed_y * (c->window / 2) <= 16384, "window too wide");
-  BE_REQ(c->goal_change_step >= 0 && c->goal_change_step < (1 << 30), "goal_change_step out of range");
-  BE_REQ(c->num_goals >= 0 && c->num_goals <= BE_MAX_GOALS, "num_goals must be in [0, 16]");
-  BE_REQ(c->num_goals >= c->num_dynamic, "need a goal per dynamic obstacle (obs_goal_position)");
-  BE_REQ(c->num_actions >= 1 && c->num_actions <= BE_MAX_ACTIONS, "num_actions must be in [1, 16]");
-  for (int k = 0; k < c->num_dynamic; ++k)
-    BE_REQ(c->obstacle_speed[k] >= -1024 && c->obstacle_speed[k] <= 1024, "obstacle speed out of range");
-  for (int g = 0; g < c->num_goals; ++g)
-    BE_REQ(c->goals[g][0] >= -16384 && c->goals[g][0] <= 16384 && c->goals[g][1] >= -16384 && c->goals[g][1] <= 16384,
-           "goal coordinates out of range");
-  for (int a = 0; a < c->num_actions; ++a)
-    BE_REQ(c->actions[a][0] >= -1024 && c->actions[a][0] <= 1024 && c->actions[a][1] >= -1024 && c->actions[a][1] <= 1024,
-           "action deltas out of range");
-  BE_REQ(c->time_limit >= 0, "time_limit must be >= 0");
-  BE_REQ(!(c->threshold_goal != c->threshold_goal), "threshold_goal is NaN");
-  {  // int16 coordinates.  The reference's dynamic obstacles are unbounded Python ints (no clamp,
-     // ballenv_env.py:334-347); here they are int16.  An obstacle spawns inside the obstacle strips
-     // and moves at most |speed| per axis per step, and with autoreset and a time limit an episode
-     // has at most time_limit moves, so the bound below holds for every episode and such a config
-     // can never leave int16.  Without that bound (time_limit 0, or autoreset 0: a caller may step
-     // past done) the kernels flag BE_STATUS_COORD_RANGE, the stored coordinate wraps (two's
-     // complement int16) and the caller must poll be_status.
-    int64_t ms = 0;
-    for (int k = 0; k < c->num_dynamic; ++k) ms = std::max<int64_t>(ms, std::abs((int64_t)c->obstacle_speed[k]));
-    const int64_t ex = std::max<int64_t>(std::abs((int64_t)c->strip_obs_x),
-                                         std::abs((int64_t)c->screen_width - c->strip_obs_x));
-    const int64_t ey = std::max<int64_t>(std::abs((int64_t)c->strip_obs_y),
-                                         std::abs((int64_t)c->screen_height - c->strip_obs_y));
-    BE_REQ(!(c->autoreset && c->time_limit > 0 && c->num_dynamic > 0) ||
-               std::max(ex, ey) + ms * (int64_t)c->time_limit <= 32767,
-           "dynamic obstacles can leave the int16 coordinate range within one episode: need "
-           "max spawn extent + max|obstacle_speed| * time_limit <= 32767 (or time_limit 0 / autoreset 0 "
-           "and poll status())");
+Launch pick_kernel(const be_config& c, int mode, bool fixed_ok, int lanes10, int lpe5, bool pool) {
+  const int W = c.window, R = c.radius_obstacle + c.radius_agent;
+  const bool fixed = mode == MODE_STEP && fixed_shape(c, fixed_ok);
+  // step2_kernel's and stepw_kernel's reset sinks store obstacles at 32-bit byte offsets: NS*N < 2^30
+  const bool off32 = (int64_t)c.num_envs * FIX_NS < (1ll << 30);
+  const char* pv = pool ? "true" : "false";
+  Launch L;
+  if (fixed && lanes10 == 2 && W == 10 && span_fits(W, R) && off32) {
+    // two lanes per env: 32 envs per wave, 128 per block
+    L.kind = KIND_STEP2; L.consumes_pool = true;
+    L.fn2 = pool ? step2_kernel<10, FIX_NS, FIX_ND, true> : step2_kernel<10, FIX_NS, FIX_ND, false>;
+    L.epb = S2_CT / 2; L.threads = S2_CT; L.lds = Step2Lds<10, FIX_NS, FIX_ND>::bytes;
+    snprintf(L.name, sizeof L.name, "step2_kernel<10, %d, %d, %s>", FIX_NS, FIX_ND, pv);
+    return L;
   }
-#undef BE_REQ
-  if (msg && msg_len > 0) msg[0] = 0;
-  return BE_OK;
-bad:
-  if (msg && msg_len > 0) snprintf(msg, (size_t)msg_len, "%s", buf);
-  return fail(nullptr, BE_E_INVALID, "invalid config: %s", buf);
+  if (fixed && W == 5 && (lpe5 == 4 || lpe5 == 8) && off32) {
+    // L lanes per env: 32 envs per block, static LDS only
+    L.kind = KIND_LANES; L.consumes_pool = true;
+    L.fn = lpe5 == 8 ? (pool ? stepw_kernel<5, FIX_NS, FIX_ND, 8, true> : stepw_kernel<5, FIX_NS, FIX_ND, 8, false>)
+                     : (pool ? stepw_kernel<5, FIX_NS, FIX_ND, 4, true> : stepw_kernel<5, FIX_NS, FIX_ND, 4, false>);
+    L.epb = 32; L.threads = 32 * lpe5;
+    snprintf(L.name, sizeof L.name, "stepw_kernel<5, %d, %d, %d, %s>", FIX_NS, FIX_ND, lpe5, pv);
+    return L;
+  }
+  if (fixed && (W == 10 || W == 5)) {
+    L.kind = KIND_FIXED1; L.consumes_pool = true;
+    L.fn = W == 10 ? (pool ? be_kernel<10, MODE_STEP, FIX_NS, FIX_ND, true> : be_kernel<10, MODE_STEP, FIX_NS, FIX_ND, false>)
+                   : (pool ? be_kernel<5, MODE_STEP, FIX_NS, FIX_ND, true> : be_kernel<5, MODE_STEP, FIX_NS, FIX_ND, false>);
+    L.lds = BeLds::bytes(FIX_NS + FIX_ND, W);
+    snprintf(L.name, sizeof L.name, "be_kernel<%d, %d, %d, %d, %s>", W, mode, FIX_NS, FIX_ND, pv);
+    return L;
+  }
+  L.kind = KIND_GENERIC;
+  int WT = W;   // the instance's compile-time W (0: run-time W, no obs stage)
+  switch (W) {
+#define BE_CASE(n) case n: L.fn = kernel_for<n>(mode); break;
+    BE_CASE(1) BE_CASE(2) BE_CASE(3) BE_CASE(4) BE_CASE(5) BE_CASE(6) BE_CASE(7) BE_CASE(8)
+    BE_CASE(9) BE_CASE(10) BE_CASE(11) BE_CASE(12) BE_CASE(13) BE_CASE(14) BE_CASE(15) BE_CASE(16)
+    BE_CASE(21)
+#undef BE_CASE
+    default: L.fn = kernel_for<0>(mode); WT = 0; break;
+  }
+  L.lds = BeLds::bytes(c.num_static + c.num_dynamic, WT);
+  snprintf(L.name, sizeof L.name, "be_kernel<%d, %d, 0, 0, false>", WT, mode);
+  return L;
 }
 
-// Can a reset re-sample the agent (ballenv_env.py:121-126, quirk Q9)?  Only if some agent spawn
-// point lies closer than min_spawn_dist to some goal spawn point: with the reference's strips
-// (agent y < 10, goal y >= 480) never.  When it cannot, prev_dist (state[2]) always equals
-// calc_dist(goal, agent) -- after a step it is that distance, after a reset total_distance -- so
-// the fixed-shape step kernels may recompute it instead of reading it (an A/B option, KParams).
-static bool q9_possible(const be_config* c) {
-  const int64_t dx = std::max<int64_t>(0, (int64_t)(c->screen_width - c->strip_goal_x) - (c->strip_agent_x - 1));
-  const int64_t dy = std::max<int64_t>(0, (int64_t)(c->screen_height - c->strip_goal_y) - (c->strip_agent_y - 1));
-  const double D = c->min_spawn_dist;
-  return D > 0.0 && sqrt((double)(dx * dx + dy * dy)) < D;
+Launch pick_rollout(const be_config& c, bool fixed_ok, int lpe5) {
+  const int R = c.radius_obstacle + c.radius_agent;
+  Launch L;
+  if (!fixed_shape(c, fixed_ok)) return L;
+  if (c.window == 5 && (lpe5 == 4 || lpe5 == 8)) {   // small batches: L lanes per env, 32-env blocks
+    L.kind = KIND_LANES;
+    L.fn = lpe5 == 8 ? rolloutw_kernel<5, FIX_NS, FIX_ND, 8> : rolloutw_kernel<5, FIX_NS, FIX_ND, 4>;
+    L.epb = 32; L.threads = 32 * lpe5;
+    snprintf(L.name, sizeof L.name, "rolloutw_kernel<5, %d, %d, %d>", FIX_NS, FIX_ND, lpe5);
+    return L;
+  }
+  if (c.window == 10) { L.fn = rollout_kernel<10, FIX_NS, FIX_ND>; L.lds = RolloutLds<10, FIX_NS, FIX_ND>::bytes(R); }
+  else if (c.window == 5) { L.fn = rollout_kernel<5, FIX_NS, FIX_ND>; L.lds = RolloutLds<5, FIX_NS, FIX_ND>::bytes(R); }
+  else return L;
+  L.kind = KIND_ROLLOUT;
+  snprintf(L.name, sizeof L.name, "rollout_kernel<%d, %d, %d, 0, 1, 10>", c.window, FIX_NS, FIX_ND);
+  return L;
 }
 
-int64_t be_step_bytes(const be_config* c) {
-  if (!c) return 0;
-  // agent R+W 8 | goal R 4 | prev_dist R+W 16 | total_dist R 8 | ep_return R+W 16 | ep_len R+W 8
-  // | episode R 4 | action R 1 | reward W 8 | done W 1                                     = 74
-  // | statics R 4*Ns | dyn xy R+W 8*Nd | dyn goal R 1*Nd | obs W 4+W^2
-  return 74 + 4ll * c->num_static + 9ll * c->num_dynamic + 4 + (int64_t)c->window * c->window;
+Launch pick_policy_rollout(const be_config& c, bool fixed_ok, int HT, int KS, int NO) {
+  const int R = c.radius_obstacle + c.radius_agent;
+  Launch L;
+  if (!fixed_shape(c, fixed_ok)) return L;
+  if (c.window == 10 && HT == 13 && KS == 2 && NO == 10) {
+    L.fn = rollout_kernel<10, FIX_NS, FIX_ND, 13, 2, 10>;
+    L.lds = RolloutLds<10, FIX_NS, FIX_ND, 13, 2, 10>::bytes(R);
+  } else if (c.window == 5 && HT == 8 && KS == 1 && NO == 10) {
+    L.fn = rollout_kernel<5, FIX_NS, FIX_ND, 8, 1, 10>;
+    L.lds = RolloutLds<5, FIX_NS, FIX_ND, 8, 1, 10>::bytes(R);
+  } else {
+    return L;
+  }
+  L.kind = KIND_POLICY_ROLLOUT;
+  snprintf(L.name, sizeof L.name, "rollout_kernel<%d, %d, %d, %d, %d, %d>", c.window, FIX_NS, FIX_ND, HT, KS, NO);
+  return L;
 }
 
-const char* be_last_error(const be_ctx* ctx) { return ctx ? ctx->err : g_err; }
-
-const char* be_kernel_name(const be_ctx* ctx, int32_t entry) {
-  static thread_local char name[48];
-  if (!ctx) return nullptr;
-  const bool fixed_ok = !ctx->generic_only && ctx->unit_moves && ctx->distinct_goals;
-  Launch L{nullptr, 0, 0, {0}};
-  switch (entry) {
-    case BE_ENTRY_STEP_ACTIONS:   // (the pool variant when the context has a pool: its state's steps run it)
-      L = pick_kernel(ctx->cfg, MODE_STEP, fixed_ok, ctx->step_lanes, ctx->step5_lpe, ctx->pool != nullptr);
-      break;
-    case BE_ENTRY_STEP_SAMPLED: L = pick_kernel(ctx->cfg, MODE_STEP, false); break;
-    case BE_ENTRY_ROLLOUT: {
-      L = pick_rollout(ctx->cfg, fixed_ok, ctx->roll5_lpe);
-      const DeviceGuard dg(ctx->device);   // fits_lds queries the context's device
-      if (dg.err != hipSuccess || !fits_lds(ctx, L)) L.fn = nullptr;
-      break;
-    }
-    case BE_ENTRY_RESET: L = pick_kernel(ctx->cfg, MODE_RESET, false); break;
-    case BE_ENTRY_OBSERVE: L = pick_kernel(ctx->cfg, MODE_OBSERVE, false); break;
-    default: return nullptr;
-  }
-  if (!L.fn && !L.fn2) return nullptr;
-  memcpy(name, L.name, sizeof name);
-  return name;
+Launch pick_pool_fill(int window) {
+  Launch L;
+  if (window != 10 && window != 5) return L;
+  L.kind = KIND_POOL_FILL;
+  L.fn = window == 10 ? pool_fill_kernel<10, FIX_NS, FIX_ND> : pool_fill_kernel<5, FIX_NS, FIX_ND>;
+  L.epb = 256; L.threads = 256;   // one lane per env, static LDS only
+  snprintf(L.name, sizeof L.name, "pool_fill_kernel<%d, %d, %d>", window, FIX_NS, FIX_ND);
+  return L;
 }
 
-int64_t be_stats_slots(const be_config* c) {
-  if (!c || c->num_envs < 1 || c->window < 1) return 0;
-  // one slot per 32 envs: the fixed-shape kernels settle stats per half-wave (LPE 1) or per
-  // wave (LPE 2), the generic ones per block (fewer slots, a prefix of these)
-  return ((int64_t)c->num_envs + 31) / 32;
+void launch_kernel(const Launch& L, const KParams& a, hipStream_t stream) {
+  const dim3 grid((unsigned)((a.n + L.epb - 1) / L.epb)), block((unsigned)L.threads);
+  if (L.fn2)
+    hipLaunchKernelGGL(L.fn2, grid, block, (size_t)L.lds, stream, a.tables, a.episode, a.ep_len, a.dyn_obs, a.dyn_goal,
+                       a.static_obs, a.n, a.gid0,
+                       KHot{a.agent, a.goal, a.prev_dist, a.total_dist, a.ep_return, a.actions, a.stats, a.prev_read,
+                            a.goal_change},
+                       a);
+  else
+    hipLaunchKernelGGL(L.fn, grid, block, (size_t)L.lds, stream, a);
 }
 
-int be_create(const be_config* cfg, int32_t device, be_ctx** out) {
-  if (!out) return fail(nullptr, BE_E_INVALID, "%s", "out is NULL");
-  *out = nullptr;
-  char msg[256];
-  if (be_config_check(cfg, msg, sizeof msg) != BE_OK) return fail(nullptr, BE_E_INVALID, "invalid config: %s", msg);
-  be_ctx* ctx = new (std::nothrow) be_ctx();
-  if (!ctx) return fail(nullptr, BE_E_NOMEM, "%s", "out of host memory");
-  ctx->cfg = *cfg;
-  ctx->device = device;
-  KParams& b = ctx->base;
-  memset(&b, 0, sizeof b);
-  b.n = cfg->num_envs; b.window = cfg->window; b.ns = cfg->num_static; b.nd = cfg->num_dynamic;
-  b.R = cfg->radius_obstacle + cfg->radius_agent; b.speed_x = cfg->speed_x; b.speed_y = cfg->speed_y;
-  b.screen_w = cfg->screen_width; b.screen_h = cfg->screen_height; b.goal_change = cfg->goal_change_step;
-  b.certainty = cfg->obs_certainty; b.time_limit = cfg->time_limit; b.num_actions = cfg->num_actions;
-  b.autoreset = cfg->autoreset; b.gid0 = (int32_t)(uint32_t)cfg->env_offset;
-  b.threshold_goal = cfg->threshold_goal; b.time_penalty = cfg->time_penalty;
-  b.static_penalty = cfg->static_penalty; b.dynamic_penalty = cfg->dynamic_penalty;
-  b.min_spawn_dist = cfg->min_spawn_dist; b.seed = cfg->seed;
-  b.num_goals = cfg->num_goals;
-  // prev_dist is read: recomputing it (possible when q9_possible() is false) measured slower, the
-  // f64 sqrt lands on the reward's chain (step2 6.52 vs 6.38 us, stepw 4.36 vs 4.20 us, A/B in one
-  // process, profiles/r03_prev_dist_ab.txt); BALLENV_PREV_READ=0 selects it where it is exact (A/B)
-  b.prev_read = 1;
-  if (const char* r = getenv("BALLENV_PREV_READ")) { if (!strcmp(r, "0") && !q9_possible(cfg)) b.prev_read = 0; }
-  ctx->unit_moves = cfg->num_actions <= 16;
-  for (int a = 0; a < cfg->num_actions && a < 16; ++a) {
-    const int mx = cfg->actions[a][0], my = cfg->actions[a][1];
-    if (mx < -1 || mx > 1 || my < -1 || my > 1) ctx->unit_moves = false;
-    else { b.amx |= (uint32_t)(mx + 1) << (2 * a); b.amy |= (uint32_t)(my + 1) << (2 * a); }
-  }
-  ctx->distinct_goals = cfg->num_goals >= 2;
-  for (int g = 0; g < cfg->num_goals; ++g)
-    for (int h = 0; h < g; ++h)
-      if (cfg->goals[g][0] == cfg->goals[h][0] && cfg->goals[g][1] == cfg->goals[h][1]) ctx->distinct_goals = false;
-  {  // smallest integer n with sqrt(n) >= min_spawn_dist (f64, correctly rounded: monotone in n)
-    const double D = cfg->min_spawn_dist;
-    long long n = D <= 0.0 ? 0 : (long long)ceil(D * D);
-    if (n > (1ll << 30)) n = 1ll << 30;
-    while (n > 0 && sqrt((double)(n - 1)) >= D) --n;
-    while (n < (1ll << 30) && sqrt((double)n) < D) ++n;
-    b.min_spawn_d2 = (int32_t)n;
-  }
-  b.inv_g1 = 1.0 / ((double)cfg->goal_change_step + 1.0);
-  if (const char* d = getenv("BALLENV_DEBUG_SKIP")) b.dbg = (int32_t)strtoul(d, nullptr, 0);
-  if (const char* g = getenv("BALLENV_GENERIC_KERNELS")) ctx->generic_only = atoi(g) != 0;
-  int cus = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) cus = 256;
-  {  // Two lanes per env (step2_kernel) shorten each wave's dependent chain where one lane per env
-     // leaves at most ~1.5 waves per SIMD; past that the one-lane kernel has the waves to hide its
-     // latency and the pair's duplicated per-env work costs more than it saves (measured on MI355X,
-     // 256 CUs: step2 6.42 / 7.51 us at 65 536 / 98 304 envs against 6.97 / 7.92; one lane 8.13 /
-     // 14.5 / 48.9 us at 131 072 / 262 144 / 2^20 against 8.54 / 16.2 / 52.6).
-     // BALLENV_STEP_LPE=1 / 2 forces one or two lanes (A/B).
-    ctx->step_lanes = (int64_t)cfg->num_envs > (int64_t)96 * 4 * cus ? 1 : 2;
-  }
-  // W = 5 (BASELINE config 2): stepw_kernel's 8 lanes per env while one lane per env would leave
-  // most of the chip idle (<= 64 envs per CU), the one-lane kernel above that.
-  ctx->step5_lpe = (int64_t)cfg->num_envs <= (int64_t)64 * cus ? 8 : 1;
-  ctx->roll5_lpe = ctx->step5_lpe;
-  if (const char* l = getenv("BALLENV_ROLLOUT5_LPE")) {   // A/B override: "1", "4" or "8", else ignored
-    if (!strcmp(l, "1")) ctx->roll5_lpe = 1;
-    else if (!strcmp(l, "4")) ctx->roll5_lpe = 4;
-    else if (!strcmp(l, "8")) ctx->roll5_lpe = 8;
-  }
-  if (const char* l = getenv("BALLENV_STEP5_LPE")) {   // A/B override: "1", "4" or "8", else ignored
-    if (!strcmp(l, "1")) ctx->step5_lpe = 1;
-    else if (!strcmp(l, "4")) ctx->step5_lpe = 4;
-    else if (!strcmp(l, "8")) ctx->step5_lpe = 8;
-  }
-  // (four lanes per env, step2_kernel<10, 13, 5, 4, 128> of commit b0bc389, was bit-exact but slower
-  // at every size: 6.08 vs 5.28 us at 32 768 envs, profiles/r04_w10_lanes_2_4.jsonl)
-  if (const char* l = getenv("BALLENV_STEP_LPE")) {   // A/B override: exactly "1" or "2", else ignored
-    if (!strcmp(l, "1")) ctx->step_lanes = 1;
-    else if (!strcmp(l, "2")) ctx->step_lanes = 2;
-  }
-  if (hipDeviceGetAttribute(&ctx->max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess ||
-      ctx->max_lds <= 0)
-    ctx->max_lds = 65536;
-  memset(&ctx->tables, 0, sizeof ctx->tables);
-  Tables& t = ctx->tables.t;
-  for (int k = 0; k < cfg->num_dynamic; ++k) t.speed[k] = cfg->obstacle_speed[k];
-  t.strip_obs_x = cfg->strip_obs_x; t.strip_obs_y = cfg->strip_obs_y;
-  t.strip_goal_x = cfg->strip_goal_x; t.strip_goal_y = cfg->strip_goal_y;
-  t.strip_agent_x = cfg->strip_agent_x; t.strip_agent_y = cfg->strip_agent_y;
-  t.radius_obstacle = cfg->radius_obstacle; t.radius_agent = cfg->radius_agent;
-  for (int g = 0; g < cfg->num_goals; ++g)
-    t.goal[g] = (int32_t)(((uint32_t)cfg->goals[g][0] & 0xFFFFu) | ((uint32_t)cfg->goals[g][1] << 16));
-  for (int a = 0; a < cfg->num_actions; ++a)
-    t.action[a] = (int32_t)(((uint32_t)cfg->actions[a][0] & 0xFFFFu) | ((uint32_t)cfg->actions[a][1] << 16));
-  for (int g = 0; g < cfg->num_goals; ++g) {  // newGoalList, ballenv_env.py:351
-    int n = 0;
-    for (int q = 0; q < cfg->num_goals; ++q)
-      if (cfg->goals[q][0] != cfg->goals[g][0] || cfg->goals[q][1] != cfg->goals[g][1]) t.other[g][n++] = (uint8_t)q;
-    t.n_other[g] = (uint8_t)n;
-  }
-  const int R = cfg->radius_obstacle + cfg->radius_agent;
-  for (int d = 0; d <= R && d <= HW_MAX; ++d) {   // exact integer sqrt
-    int h = 0;
-    while ((h + 1) * (h + 1) <= R * R - d * d) ++h;
-    t.hw[d] = (uint8_t)h;
-  }
-  if (span_fits(cfg->window, R)) {   // step2_kernel's row-span table (TablesX)
-    const int W = cfg->window, C = W - 1 + R, J0 = R + W - 2;   // K = W-1 rows
-    for (int j = 0; j < SPAN_N; ++j) {
-      const int a = abs(j - J0), hw = a <= R ? t.hw[a] : 0;
-      ctx->tables.span[j] = a <= R && j <= 2 * J0 ? ((2ull << (2 * hw)) - 1ull) << (C - hw) : 0ull;
-    }
-  }
-  const DeviceGuard dg(device);   // the caller's current device is restored on return
-  hipError_t e = dg.err;
-  if (e == hipSuccess) e = hipMalloc(&ctx->status, sizeof(int));
-  if (e == hipSuccess) e = hipMemset(ctx->status, 0, sizeof(int));
-  if (e == hipSuccess) e = hipMalloc(&ctx->d_tables, sizeof(TablesX));
-  if (e == hipSuccess) e = hipMemcpy(ctx->d_tables, &ctx->tables, sizeof(TablesX), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  // be_step's two possible kernels, picked once (pick_kernel formats a name: not per launch)
-  ctx->step_launch[0] = pick_kernel(ctx->cfg, MODE_STEP, false, ctx->step_lanes, ctx->step5_lpe);
-  ctx->step_launch[1] = pick_kernel(ctx->cfg, MODE_STEP, true, ctx->step_lanes, ctx->step5_lpe);
-  {  // the autoreset pool, for the fixed-shape kernels that consume it (step2_kernel, stepw_kernel, the one-lane kernel)
-    const KFn f = ctx->step_launch[1].fn;
-    const KFn2 f2 = ctx->step_launch[1].fn2;
-    int64_t onelane_max = (int64_t)2 * 64 * 4 * cus;   // BALLENV_POOL_ONELANE_MAX: the bound below, for A/B runs
-    if (const char* v = getenv("BALLENV_POOL_ONELANE_MAX")) onelane_max = atoll(v);
-    const bool consumes = ctx->unit_moves && ctx->distinct_goals && !ctx->generic_only && cfg->autoreset &&
-                          (f2 == step2_kernel<10, FIX_NS, FIX_ND, false> || f == stepw_kernel<5, FIX_NS, FIX_ND, 8, false> ||
-                           f == stepw_kernel<5, FIX_NS, FIX_ND, 4, false> ||
-                           // the one-lane kernel up to two waves per SIMD: 7.51-7.59 against 7.76-7.85 us at
-                           // 131 072 envs; at 262 144 (four waves per SIMD hide the reset draws, and the
-                           // fill costs more) 14.11-14.24 against 13.71-13.72 (profiles/r06_onelane_pool_ab.txt)
-                           ((f == be_kernel<10, MODE_STEP, FIX_NS, FIX_ND> || f == be_kernel<5, MODE_STEP, FIX_NS, FIX_ND>) &&
-                            (int64_t)cfg->num_envs <= onelane_max));
-    bool want = consumes && (int64_t)cfg->num_envs <= POOL_MAX_ENVS;
-    if (const char* v = getenv("BALLENV_POOL")) want = want && strcmp(v, "0") != 0;   // A/B: "0" = no pool
-    ctx->pool_period = 128;
-    if (const char* v = getenv("BALLENV_POOL_PERIOD")) ctx->pool_period = std::max(0, atoi(v));
-    if (want && e == hipSuccess) {
-      ctx->pool_bytes = pool_bytes_per_env(FIX_NS, FIX_ND) * cfg->num_envs;
-      ctx->pool_fill = cfg->window == 10 ? pool_fill_kernel<10, FIX_NS, FIX_ND> : pool_fill_kernel<5, FIX_NS, FIX_ND>;
-      e = hipMalloc(&ctx->pool, (size_t)ctx->pool_bytes);
-      if (e == hipSuccess) e = hipMemset(ctx->pool, 0, (size_t)ctx->pool_bytes);   // every entry unwritten
-      if (e == hipSuccess) e = hipDeviceSynchronize();
-      ctx->step_launch_pool = pick_kernel(ctx->cfg, MODE_STEP, true, ctx->step_lanes, ctx->step5_lpe, true);
-    }
-  }
-  if (e != hipSuccess) {
-    int rc = fail(nullptr, BE_E_HIP, "HIP error in be_create: %s", hipGetErrorString(e));
-    if (ctx->status) (void)hipFree(ctx->status);
-    if (ctx->d_tables) (void)hipFree(ctx->d_tables);
-    if (ctx->pool) (void)hipFree(ctx->pool);
-    delete ctx;
-    return rc;
-  }
-  *out = ctx;
-  return BE_OK;
-}
-
-int be_destroy(be_ctx* ctx) {
-  if (!ctx) return BE_OK;
-  const DeviceGuard dg(ctx->device);   // the caller's current device is restored on return
-  if (ctx->status) (void)hipFree(ctx->status);
-  if (ctx->d_tables) (void)hipFree(ctx->d_tables);
-  if (ctx->pool) (void)hipFree(ctx->pool);
-  delete ctx;
-  return BE_OK;
-}
-
-static int check_state(be_ctx* ctx, const be_state* st) {
-  if (!st || !st->agent || !st->goal || !st->prev_dist || !st->total_dist || !st->ep_return || !st->ep_len ||
-      !st->episode)
-    return fail(ctx, BE_E_INVALID, "%s", "be_state has a NULL pointer");
-  if (ctx->cfg.num_static > 0 && !st->static_obs) return fail(ctx, BE_E_INVALID, "%s", "static_obs is NULL");
-  if (ctx->cfg.num_dynamic > 0 && (!st->dyn_obs || !st->dyn_goal))
-    return fail(ctx, BE_E_INVALID, "%s", "dyn_obs/dyn_goal is NULL");
-  return BE_OK;
-}
-
-// Per-call KParams: the context's config part + this call's pointers.
-static KParams make_params(be_ctx* ctx, const be_state* st, const be_out* out) {
-  KParams a = ctx->base;
-  a.agent = st->agent; a.goal = st->goal; a.prev_dist = st->prev_dist; a.total_dist = st->total_dist;
-  a.ep_return = st->ep_return; a.ep_len = st->ep_len; a.episode = st->episode; a.static_obs = st->static_obs;
-  a.dyn_obs = st->dyn_obs; a.dyn_goal = st->dyn_goal;
-  if (out) {
-    a.obs = out->obs; a.obs_f32 = out->obs_f32; a.reward = out->reward; a.done = out->done;
-    a.truncated = out->truncated; a.terminal_obs = out->terminal_obs; a.final_return = out->final_return;
-    a.final_len = out->final_len; a.stats = out->stats;
-  }
-  a.tables = &ctx->d_tables->t;
-  a.status = ctx->status;
-  return a;
-}
-
-// pool_fill_kernel over every env of the state (the caller holds the DeviceGuard)
-static void launch_pool_fill(be_ctx* ctx, const KParams& a, void* stream) {
-  KParams f = a;
-  f.pool = ctx->pool;
-  const int N = ctx->cfg.num_envs;
-  hipLaunchKernelGGL(ctx->pool_fill, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, f);
-  ctx->pool_calls = 0;
-}
-
-// steps > 1 (be_step_n): `steps` launches of the same kernel, actions advancing by N per step.
-static int launch(be_ctx* ctx, int mode, KParams& a, void* stream, int32_t steps = 1) {
-  const bool fixed_ok = mode == MODE_STEP && a.tape == nullptr && a.actions != nullptr && !ctx->generic_only &&
-                        ctx->unit_moves && ctx->distinct_goals;
-  if (((uintptr_t)a.obs & 15) || ((uintptr_t)a.obs_f32 & 15))
-    return fail(ctx, BE_E_INVALID, "%s", "obs / obs_f32 must be 16-byte aligned");
-  const DeviceGuard dg(ctx->device);   // the caller's current device is restored on return
-  HIP_TRY(ctx, dg.err);
-  // the pool serves one state (its owner: the state last reset / loaded, else the first one stepped);
-  // a step of any other state draws its resets inline, so a context's entries are only ever written
-  // and read by the launches of one state, which the caller orders on its stream anyway
-  if (ctx->pool && mode == MODE_STEP && fixed_ok && !ctx->pool_owner) ctx->pool_owner = a.episode;
-  const bool use_pool = ctx->pool && mode == MODE_STEP && fixed_ok && a.episode == ctx->pool_owner;
-  a.pool = use_pool ? ctx->pool : nullptr;
-  const Launch L = mode == MODE_STEP ? (use_pool ? ctx->step_launch_pool : ctx->step_launch[fixed_ok ? 1 : 0])
-                                     : pick_kernel(ctx->cfg, mode, fixed_ok, ctx->step_lanes, ctx->step5_lpe);
-  const int N = ctx->cfg.num_envs;
-  const dim3 grid((unsigned)((N + L.epb - 1) / L.epb)), block((unsigned)L.threads);
-  for (int32_t s = 0; s < steps; ++s) {
-    if (L.fn2)
-      hipLaunchKernelGGL(L.fn2, grid, block, (size_t)L.lds, (hipStream_t)stream, a.tables, a.episode, a.ep_len, a.dyn_obs,
-                         a.dyn_goal, a.static_obs, a.n, a.gid0,
-                         KHot{a.agent, a.goal, a.prev_dist, a.total_dist, a.ep_return, a.actions, a.stats, a.prev_read,
-                              a.goal_change},
-                         a);
-    else
-      hipLaunchKernelGGL(L.fn, grid, block, (size_t)L.lds, (hipStream_t)stream, a);
-    a.actions += N;
-    if (use_pool && ctx->pool_period > 0 && ++ctx->pool_calls >= ctx->pool_period) launch_pool_fill(ctx, a, stream);
-  }
-  HIP_TRY(ctx, hipGetLastError());
-  return BE_OK;
-}
-
-int be_reset(be_ctx* ctx, const be_state* st, const uint8_t* mask, const int16_t* reset_tape, int32_t tape_len,
-             const be_out* out, void* stream) {
-  if (!ctx) return fail(nullptr, BE_E_INVALID, "%s", "ctx is NULL");
-  if (int rc = check_state(ctx, st)) return rc;
-  if (reset_tape && tape_len < 0) return fail(ctx, BE_E_INVALID, "%s", "tape_len < 0");
-  if (!out || (!out->obs && !out->obs_f32)) return fail(ctx, BE_E_INVALID, "%s", "be_reset needs out->obs or out->obs_f32");
-  KParams a = make_params(ctx, st, out);
-  a.reward = nullptr; a.done = nullptr; a.truncated = nullptr; a.terminal_obs = nullptr;
-  a.final_return = nullptr; a.final_len = nullptr; a.stats = nullptr;
-  a.mask = mask; a.reset_tape = reset_tape; a.reset_tape_len = reset_tape ? tape_len : 0;
-  if (int rc = launch(ctx, MODE_RESET, a, stream)) return rc;
-  if (ctx->pool) {   // this state's next two episodes per env, ahead of its first step
-    ctx->pool_owner = st->episode;
-    const DeviceGuard dg(ctx->device);
-    HIP_TRY(ctx, dg.err);
-    launch_pool_fill(ctx, a, stream);
-    HIP_TRY(ctx, hipGetLastError());
-  }
-  return BE_OK;
-}
-
-int be_step(be_ctx* ctx, const be_state* st, const uint8_t* actions, const int16_t* action_deltas,
-            const int16_t* draw_tape, const be_out* out, void* stream) {
-  if (!ctx) return fail(nullptr, BE_E_INVALID, "%s", "ctx is NULL");
-  if (int rc = check_state(ctx, st)) return rc;
-  if (!out || !out->reward || !out->done) return fail(ctx, BE_E_INVALID, "%s", "be_step needs out->reward and out->done");
-  if (draw_tape && ctx->cfg.autoreset) return fail(ctx, BE_E_INVALID, "%s", "draw tapes (parity mode) need autoreset = 0");
-  KParams a = make_params(ctx, st, out);
-  a.actions = actions; a.deltas = action_deltas; a.tape = draw_tape;
-  return launch(ctx, MODE_STEP, a, stream);
-}
-
-int be_step_n(be_ctx* ctx, const be_state* st, const uint8_t* actions, int32_t steps, const be_out* out,
-              void* stream) {
-  if (!ctx) return fail(nullptr, BE_E_INVALID, "%s", "ctx is NULL");
-  if (int rc = check_state(ctx, st)) return rc;
-  if (!actions || steps < 0) return fail(ctx, BE_E_INVALID, "%s", "be_step_n needs actions and steps >= 0");
-  if (!out || !out->reward || !out->done) return fail(ctx, BE_E_INVALID, "%s", "be_step_n needs out->reward and out->done");
-  if (steps == 0) return BE_OK;
-  KParams a = make_params(ctx, st, out);
-  a.actions = actions;
-  return launch(ctx, MODE_STEP, a, stream, steps);
-}
-
-int be_rollout(be_ctx* ctx, const be_state* st, const uint8_t* actions, int32_t steps, const be_out* out,
-               void* stream) {
-  if (!ctx) return fail(nullptr, BE_E_INVALID, "%s", "ctx is NULL");
-  if (int rc = check_state(ctx, st)) return rc;
-  if (!actions || steps < 0) return fail(ctx, BE_E_INVALID, "%s", "be_rollout needs actions and steps >= 0");
-  if (!out || !out->obs || !out->reward || !out->done)
-    return fail(ctx, BE_E_INVALID, "%s", "be_rollout needs out->obs, out->reward and out->done");
-  if (out->obs_f32) return fail(ctx, BE_E_INVALID, "%s", "be_rollout writes u8 obs only (obs_f32 must be NULL)");
-  const int64_t N = ctx->cfg.num_envs, F = 4 + (int64_t)ctx->cfg.window * ctx->cfg.window;
-  if (((uintptr_t)out->obs & 15) || (N * F) % 16)
-    return fail(ctx, BE_E_INVALID, "%s", "be_rollout needs a 16-byte aligned obs and num_envs * (4+W*W) % 16 == 0");
-  if (steps == 0) return BE_OK;
-  const Launch L = pick_rollout(ctx->cfg, !ctx->generic_only && ctx->unit_moves && ctx->distinct_goals, ctx->roll5_lpe);
-  bool fused = false;
-  {   // every HIP query (fits_lds' function attributes) on the context's device
-    const DeviceGuard dg(ctx->device);   // the caller's current device is restored on return
-    HIP_TRY(ctx, dg.err);
-    fused = fits_lds(ctx, L);
-  }
-  if (fused) {
-    KParams a = make_params(ctx, st, out);
-    a.actions = actions; a.steps = steps;
-    const DeviceGuard dg(ctx->device);   // the caller's current device is restored on return
-    HIP_TRY(ctx, dg.err);
-    const dim3 grid((unsigned)((N + L.epb - 1) / L.epb)), block((unsigned)L.threads);
-    hipLaunchKernelGGL(L.fn, grid, block, (size_t)L.lds, (hipStream_t)stream, a);
-    HIP_TRY(ctx, hipGetLastError());
-    return BE_OK;
-  }
-  // any other config: one be_step per step into the (steps, N, ...) slices (same results)
-  for (int32_t s = 0; s < steps; ++s) {
-    be_out o = *out;
-    o.obs = out->obs + s * N * F;
-    o.reward = out->reward + s * N;
-    o.done = out->done + s * N;
-    if (o.truncated) o.truncated = out->truncated + s * N;
-    if (o.terminal_obs) o.terminal_obs = out->terminal_obs + s * N * F;
-    if (o.final_return) o.final_return = out->final_return + s * N;
-    if (o.final_len) o.final_len = out->final_len + s * N;
-    if (int rc = be_step(ctx, st, actions + s * N, nullptr, nullptr, &o, stream)) return rc;
-  }
-  return BE_OK;
-}
-
-}  // extern "C"
-
-int be_internal_policy_rollout(be_ctx* ctx, const be_state* st, const be_pol_rollout_args* r, void* stream) {
-  const Launch L = pick_policy_rollout(ctx->cfg, !ctx->generic_only && ctx->unit_moves && ctx->distinct_goals, r->HT,
-                                       r->KS, r->NO);
-  const DeviceGuard dg(ctx->device);   // the caller's current device is restored on return; every
-  HIP_TRY(ctx, dg.err);                // HIP query below (fits_lds) runs on the context's device
-  if (!fits_lds(ctx, L)) return 0;   // the caller loops select_action + be_step instead
-  KParams a = make_params(ctx, st, r->out);
-  a.steps = r->steps;
-  a.pol_bytes = r->img_bytes; a.pol_actions = r->num_actions; a.pol_img = r->img; a.pol_seed = r->seed;
-  a.obs_in = r->obs_in; a.obs_last = r->obs_last;
-  a.act_out = r->act->action; a.logp_out = r->act->log_prob; a.value_out = r->act->value;
-  const int N = ctx->cfg.num_envs;
-  const dim3 grid((unsigned)((N + L.epb - 1) / L.epb)), block((unsigned)BLOCK_THREADS);
-  hipLaunchKernelGGL(L.fn, grid, block, (size_t)L.lds, (hipStream_t)stream, a);
-  HIP_TRY(ctx, hipGetLastError());
-  return 1;
-}
-
-extern "C" {
-
-int be_observe(be_ctx* ctx, const be_state* st, const be_out* out, void* stream) {
-  if (!ctx) return fail(nullptr, BE_E_INVALID, "%s", "ctx is NULL");
-  if (int rc = check_state(ctx, st)) return rc;
-  if (!out || (!out->obs && !out->obs_f32)) return fail(ctx, BE_E_INVALID, "%s", "be_observe needs out->obs or out->obs_f32");
-  KParams a = make_params(ctx, st, out);
-  a.reward = nullptr; a.done = nullptr; a.truncated = nullptr; a.terminal_obs = nullptr;
-  a.final_return = nullptr; a.final_len = nullptr; a.stats = nullptr;
-  return launch(ctx, MODE_OBSERVE, a, stream);
-}
-
-int be_sample_actions(be_ctx* ctx, uint8_t* actions_out, int32_t steps, uint64_t seed, void* stream) {
-  if (!ctx || !actions_out || steps < 0) return fail(ctx, BE_E_INVALID, "%s", "bad arguments to be_sample_actions");
-  if (steps == 0) return BE_OK;
-  const DeviceGuard dg(ctx->device);   // the caller's current device is restored on return
-  HIP_TRY(ctx, dg.err);
-  const int64_t total = (int64_t)ctx->cfg.num_envs * steps;
+void launch_sample_actions(uint8_t* out, int32_t n, int32_t steps, int64_t env_offset, int32_t num_actions,
+                           unsigned long long seed, hipStream_t stream) {
+  const int64_t total = (int64_t)n * steps;
   int64_t blocks = (total + 255) / 256;
   if (blocks > 65536) blocks = 65536;
-  hipLaunchKernelGGL(sample_actions_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, actions_out,
-                     ctx->cfg.num_envs, steps, ctx->cfg.env_offset, ctx->cfg.num_actions, (unsigned long long)seed);
-  HIP_TRY(ctx, hipGetLastError());
-  return BE_OK;
+  hipLaunchKernelGGL(sample_actions_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, out, n, steps, env_offset,
+                     num_actions, seed);
 }
 
-// ---- env-state checkpoint: header + the be_state arrays at 16-byte aligned offsets
-struct BlobLayout { int64_t off[10], bytes[10], total; };
-static BlobLayout blob_layout(const be_config* c) {
-  BlobLayout b;
-  const int64_t N = c->num_envs, ns = c->num_static, nd = c->num_dynamic;
-  const int64_t sz[10] = {4 * N, 4 * N, 8 * N, 8 * N, 8 * N, 4 * N, 4 * N, 4 * ns * N, 4 * nd * N, nd * N};
-  int64_t o = 64;
-  for (int k = 0; k < 10; ++k) { b.off[k] = o; b.bytes[k] = sz[k]; o += (sz[k] + 15) & ~15ll; }
-  b.total = o;
-  return b;
-}
-static void blob_header(const be_config* c, int64_t total, int64_t (&hdr)[8]) {
-  memset(hdr, 0, sizeof hdr);
-  memcpy(&hdr[0], "BALLENV1", 8);
-  hdr[1] = BE_ABI_VERSION; hdr[2] = c->num_envs; hdr[3] = c->num_static; hdr[4] = c->num_dynamic; hdr[5] = total;
-}
-static void state_ptrs(const be_state* st, void* (&p)[10]) {
-  p[0] = st->agent; p[1] = st->goal; p[2] = st->prev_dist; p[3] = st->total_dist; p[4] = st->ep_return;
-  p[5] = st->ep_len; p[6] = st->episode; p[7] = st->static_obs; p[8] = st->dyn_obs; p[9] = st->dyn_goal;
-}
+}  // namespace bestep
 
-int64_t be_state_blob_bytes(const be_config* cfg) {
-  if (!cfg || cfg->num_envs < 1) return 0;
-  return blob_layout(cfg).total;
-}
-
-int be_save_state(be_ctx* ctx, const be_state* st, void* blob, void* stream) {
-  if (!ctx) return fail(nullptr, BE_E_INVALID, "%s", "ctx is NULL");
-  if (int rc = check_state(ctx, st)) return rc;
-  if (!blob) return fail(ctx, BE_E_INVALID, "%s", "blob is NULL");
-  const DeviceGuard dg(ctx->device);   // the caller's current device is restored on return
-  HIP_TRY(ctx, dg.err);
-  const BlobLayout L = blob_layout(&ctx->cfg);
-  blob_header(&ctx->cfg, L.total, ctx->blob_hdr);   // lives in the context: safe for an async copy
-  hipStream_t s = (hipStream_t)stream;
-  HIP_TRY(ctx, hipMemcpyAsync(blob, ctx->blob_hdr, sizeof ctx->blob_hdr, hipMemcpyDefault, s));
-  void* src[10];
-  state_ptrs(st, src);
-  for (int k = 0; k < 10; ++k)
-    if (L.bytes[k] > 0)
-      HIP_TRY(ctx, hipMemcpyAsync(static_cast<char*>(blob) + L.off[k], src[k], (size_t)L.bytes[k], hipMemcpyDefault, s));
-  return BE_OK;
-}
-
-int be_load_state(be_ctx* ctx, const be_state* st, const void* blob, void* stream) {
-  if (!ctx) return fail(nullptr, BE_E_INVALID, "%s", "ctx is NULL");
-  if (int rc = check_state(ctx, st)) return rc;
-  if (!blob) return fail(ctx, BE_E_INVALID, "%s", "blob is NULL");
-  const DeviceGuard dg(ctx->device);   // the caller's current device is restored on return
-  HIP_TRY(ctx, dg.err);
-  const BlobLayout L = blob_layout(&ctx->cfg);
-  hipStream_t s = (hipStream_t)stream;
-  int64_t got[8], want[8];
-  HIP_TRY(ctx, hipMemcpyAsync(got, blob, sizeof got, hipMemcpyDefault, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
-  blob_header(&ctx->cfg, L.total, want);
-  if (memcmp(got, want, sizeof got) != 0)
-    return fail(ctx, BE_E_INVALID, "%s", "state blob header does not match this context (magic, ABI, N, Ns, Nd)");
-  void* dst[10];
-  state_ptrs(st, dst);
-  for (int k = 0; k < 10; ++k)
-    if (L.bytes[k] > 0)
-      HIP_TRY(ctx, hipMemcpyAsync(dst[k], static_cast<const char*>(blob) + L.off[k], (size_t)L.bytes[k], hipMemcpyDefault, s));
-  if (ctx->pool) {   // the loaded episodes' next entries (the pool's entries need no invalidation:
-                     // each is a pure function of (seed, global id, episode) and is checked by its tag)
-    ctx->pool_owner = st->episode;
-    launch_pool_fill(ctx, make_params(ctx, st, nullptr), stream);
-    HIP_TRY(ctx, hipGetLastError());
-  }
-  return BE_OK;
-}
-
-int be_pool_fill(be_ctx* ctx, const be_state* st, void* stream) {
-  if (!ctx) return fail(nullptr, BE_E_INVALID, "%s", "ctx is NULL");
-  if (int rc = check_state(ctx, st)) return rc;
-  if (!ctx->pool) return BE_OK;
-  const DeviceGuard dg(ctx->device);
-  HIP_TRY(ctx, dg.err);
-  ctx->pool_owner = st->episode;
-  launch_pool_fill(ctx, make_params(ctx, st, nullptr), stream);
-  HIP_TRY(ctx, hipGetLastError());
-  return BE_OK;
-}
-
-int be_pool_invalidate(be_ctx* ctx, void* stream) {
-  if (!ctx) return fail(nullptr, BE_E_INVALID, "%s", "ctx is NULL");
-  if (!ctx->pool) return BE_OK;
-  const DeviceGuard dg(ctx->device);
-  HIP_TRY(ctx, dg.err);
-  HIP_TRY(ctx, hipMemsetAsync(ctx->pool, 0, (size_t)ctx->pool_bytes, (hipStream_t)stream));
-  return BE_OK;
-}
-
-int be_pool_set_period(be_ctx* ctx, int32_t period) {
-  if (!ctx) return fail(nullptr, BE_E_INVALID, "%s", "ctx is NULL");
-  if (period < 0) return fail(ctx, BE_E_INVALID, "%s", "pool period must be >= 0");
-  ctx->pool_period = period;
-  ctx->pool_calls = 0;
-  return BE_OK;
-}
-
-int64_t be_pool_bytes(const be_ctx* ctx) { return ctx && ctx->pool ? ctx->pool_bytes : 0; }
-
-int32_t be_pool_period(const be_ctx* ctx) { return ctx ? ctx->pool_period : 0; }
-
-int be_pool_entry(be_ctx* ctx, int32_t env, int32_t slot, uint32_t* words, double* f64, int32_t write) {
-  if (!ctx) return fail(nullptr, BE_E_INVALID, "%s", "ctx is NULL");
-  if (!ctx->pool) return fail(ctx, BE_E_INVALID, "%s", "this context has no autoreset pool");
-  if (env < 0 || env >= ctx->cfg.num_envs || slot < 0 || slot > 1 || !words || !f64)
-    return fail(ctx, BE_E_INVALID, "%s", "bad arguments to be_pool_entry");
-  const DeviceGuard dg(ctx->device);
-  HIP_TRY(ctx, dg.err);
-  HIP_TRY(ctx, hipDeviceSynchronize());
-  // the header's word order (TAG, AGENT, GOAL, ROWS0 | flags << 30, ROWS1, ROWS2, obstacles) from / to
-  // the tags array and the entry body
-  const int64_t n = ctx->cfg.num_envs, x = (int64_t)slot * n + env;
-  constexpr int NBW = pool_body_words(FIX_NS, FIX_ND), NO = FIX_NS + FIX_ND;
-  char* tv = reinterpret_cast<char*>(ctx->pool) + x * 8;
-  char* body = reinterpret_cast<char*>(ctx->pool) + 16 * n + x * 4 * NBW;
-  uint32_t t[2], b[NBW];
-  HIP_TRY(ctx, hipMemcpy(t, tv, sizeof t, hipMemcpyDeviceToHost));
-  HIP_TRY(ctx, hipMemcpy(b, body, sizeof b, hipMemcpyDeviceToHost));
-  if (!write) {
-    words[0] = t[0]; words[1] = b[PB_AGENT]; words[2] = b[PB_GOAL];
-    words[3] = (b[PB_ROWS] & 0x3FFFFFFFu) | ((t[1] & 3u) << 30);
-    words[4] = b[PB_ROWS + 1]; words[5] = b[PB_ROWS + 2];
-    for (int k = 0; k < NO; ++k) words[6 + k] = b[PB_OBS + k];
-    memcpy(&f64[0], &b[PB_PREV], 8);
-    memcpy(&f64[1], &b[PB_TOTAL], 8);
-    return BE_OK;
-  }
-  t[0] = words[0]; t[1] = (words[3] >> 30) & 3u;
-  b[PB_AGENT] = words[1]; b[PB_GOAL] = words[2];
-  b[PB_ROWS] = words[3] & 0x3FFFFFFFu; b[PB_ROWS + 1] = words[4]; b[PB_ROWS + 2] = words[5];
-  for (int k = 0; k < NO; ++k) b[PB_OBS + k] = words[6 + k];
-  memcpy(&b[PB_PREV], &f64[0], 8);
-  memcpy(&b[PB_TOTAL], &f64[1], 8);
-  HIP_TRY(ctx, hipMemcpy(tv, t, sizeof t, hipMemcpyHostToDevice));
-  HIP_TRY(ctx, hipMemcpy(body, b, sizeof b, hipMemcpyHostToDevice));
-  return BE_OK;
-}
-
-int be_status(be_ctx* ctx, int32_t* status_out, void* stream) {
-  if (!ctx || !status_out) return fail(ctx, BE_E_INVALID, "%s", "bad arguments to be_status");
-  const DeviceGuard dg(ctx->device);   // the caller's current device is restored on return
-  HIP_TRY(ctx, dg.err);
-  HIP_TRY(ctx, hipStreamSynchronize((hipStream_t)stream));
-  int v = 0;
-  HIP_TRY(ctx, hipMemcpy(&v, ctx->status, sizeof v, hipMemcpyDeviceToHost));
-  const int zero = 0;
-  HIP_TRY(ctx, hipMemcpy(ctx->status, &zero, sizeof zero, hipMemcpyHostToDevice));
-  *status_out = v;
-  return BE_OK;
-}
-
+extern "C" {
+BE_DIAG_STEP_ENTRIES   // diagnostics builds only (diag.h): the stamp tables live in this unit
 }  // extern "C"

@@ -10,8 +10,10 @@
 // Outputs of a diagnostics build are wrong whenever a skip bit is set.
 //
 // A translation unit selects its section before including: BE_DIAG_UNIT_STEP (csrc/ballenv.hip,
-// inside its anonymous namespace) or BE_DIAG_UNIT_BOARD (csrc/board.hip); each unit then expands
-// its BE_DIAG_*_ENTRIES macro inside its extern "C" block.
+// inside its anonymous namespace, ahead of the kernels that use the hooks) or
+// BE_DIAG_UNIT_BOARD (csrc/board.hip); each unit then expands its BE_DIAG_*_ENTRIES macro inside an
+// extern "C" block (ballenv.hip's holds nothing else: the step engine's other entry points are in
+// csrc/abi.hip, but the stamp tables live in the unit of the kernels that write them).
 #pragma once
 
 #if defined(BE_DIAG_UNIT_STEP)

@@ -265,7 +265,7 @@ int64_t be_pool_bytes(const be_ctx* ctx);
 /* Test hook (synchronous; device-wide sync first): read (write = 0) or overwrite (write = 1) env's
  * entry in slot (0 / 1: the slot of episode x is x & 1).  words: TAG, AGENT, GOAL, ROWS0..2, then
  * the NS + ND obstacles' packed xy (6 + 13 + 5 words); f64: PREV, TOTAL.  ROWS0 bit 30 marks a
- * written entry, bit 31 a rejection-limit hit (layout: csrc/ballenv.hip, "the autoreset pool"). */
+ * written entry, bit 31 a rejection-limit hit (layout: csrc/step_types.h, "the autoreset pool"). */
 int be_pool_entry(be_ctx* ctx, int32_t env, int32_t slot, uint32_t* words, double* f64, int32_t write);
 
 /* ---- on-GPU select_action for batched rollouts (BASELINE config 5) ----

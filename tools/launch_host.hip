@@ -10,7 +10,7 @@
 #include <vector>
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP %s at %d\n", hipGetErrorString(e), __LINE__); return 1; } } while (0)
 
-struct KP {   // the size of ballenv.hip's KParams
+struct KP {   // the size of the step kernels' KParams (csrc/step_types.h)
   void* ptr[40];
   int flag;
   int pad[15];

@@ -4,12 +4,11 @@
 # Build here first: BUILD=1 bash tools/stamps_run.sh (no GPU needed).
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
-F="-O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math --offload-arch=gfx950 -I include -I gym-ballenv_amd/csrc"
+F="-O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math --offload-arch=gfx950 -I include"
 ST=${ST:-diag/st}   # under tools/ (tools/diag is not pushed to the box: ST=stlib for a box run, deleted after)
 if [ "${BUILD:-0}" = "1" ]; then
-  mkdir -p tools/$ST
-  /opt/rocm/bin/hipcc $F -shared -DBE_DIAG_STAMPS gym-ballenv_amd/csrc/ballenv.hip gym-ballenv_amd/csrc/policy.hip \
-      gym-ballenv_amd/csrc/features.hip gym-ballenv_amd/csrc/board.hip -o tools/$ST/libballenv.so || exit 1
+  bash tools/build_ab_lib.sh st -DBE_DIAG_STAMPS || exit 1   # every unit, with build.py's per-unit flags
+  [ "$ST" = diag/st ] || { mkdir -p tools/$ST && cp tools/diag/st/libballenv.so tools/$ST/libballenv.so; } || exit 1
   /opt/rocm/bin/hipcc $F tools/stamps.hip -Ltools/$ST -lballenv -Wl,-rpath,"\$ORIGIN/$ST" -o tools/stamps || exit 1
   echo built; exit 0
 fi
