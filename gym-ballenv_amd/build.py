@@ -13,6 +13,9 @@ object) and linked into one shared library:
   csrc/features.hip sibling observation formats (prep_state2 block counts)
   csrc/board.hip    the createBoard physics profile + featureExtractor
   csrc/a2c.hip      A2C targets of a recorded rollout (the batched finish_episode)
+  csrc/a2c_grad.hip A2C losses and Policy gradients of recorded rows (f32 MFMAs; no VGPR_MFMA:
+                    its accumulators live for the whole kernel, and with them in VGPRs the W = 10
+                    instance measured 14 % slower, W = 5 the same: profiles/a2c_grad_ab.json)
 """
 from __future__ import annotations
 
@@ -38,7 +41,7 @@ VGPR_MFMA = ["-mllvm", "-amdgpu-mfma-vgpr-form"]
 # prologue); the compiler keeps an s_load entry for firmware without the preload.
 KARG_PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
 UNITS = {"ballenv.hip": [*VGPR_MFMA, *KARG_PRELOAD], "abi.hip": [], "policy.hip": ["-fno-slp-vectorize", *VGPR_MFMA],
-         "features.hip": [], "board.hip": [], "a2c.hip": []}
+         "features.hip": [], "board.hip": [], "a2c.hip": [], "a2c_grad.hip": []}
 HEADERS = [HDR, *(os.path.join(CSRC, h) for h in ("philox.h", "internal.h", "policy_core.h", "diag.h", "step_types.h"))]
 
 

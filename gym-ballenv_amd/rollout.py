@@ -27,6 +27,8 @@ recursion (:224-227) with episode boundaries (done) cutting the sum;
 ``a2c_losses`` / ``a2c_update`` are the whole finish_episode (per-episode
 return normalisation, policy + value losses) over all envs at once, so a
 training loop is rollout (HIP) -> update (torch autograd) -> re-pack (HIP).
+``A2CGrad`` (``a2c_update(grads="hip")``) is the losses and ``loss.backward()``
+of that update in one HIP entry (``be_a2c_grad``), straight from the u8 record.
 """
 from __future__ import annotations
 
@@ -90,6 +92,86 @@ def a2c_targets_into(env, rewards, dones, values, gamma: float, eps: float, boot
     if rc:
         _abi.check(rc, env._ctx)
     return out
+
+
+_PARAMS = ("fc1.weight", "fc1.bias", "action_head.weight", "action_head.bias", "value_head.weight",
+           "value_head.bias")
+
+
+class A2CGrad:
+    """``be_a2c_grad`` bound to one BatchedBallEnv and one Policy: the policy and value loss sums of
+    ``a2c_losses`` and what ``loss.backward()`` leaves in the six ``.grad``, from the recorded u8
+    observations in two launches (include/ballenv.h pins the arithmetic; reproducible bit for bit).
+
+    Owns the workspace, the six gradient tensors (``.grads``, keyed like ``policy.state_dict()``)
+    and the f64 ``losses``; nothing is allocated per call, so a call can be graph-captured.  The
+    weights are read from the module's parameters at call time (fp32, contiguous, on the env's
+    device)."""
+
+    def __init__(self, env, policy: Policy):
+        self.env, self.policy = env, policy
+        self._lib = _abi.lib()
+        dev = env.device
+        self.hidden, self.num_actions = int(policy.hidden_layer), int(policy.action_head.out_features)
+        if policy.fc1.in_features != env.obs_dim:
+            raise ValueError("policy input size does not match the env's observation")
+        nbytes = int(self._lib.be_a2c_grad_workspace_bytes(env._ctx, self.hidden, self.num_actions))
+        if nbytes < 0:
+            _abi.check(nbytes, env._ctx)
+        self.workspace = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+        sd = policy.state_dict()
+        self.grads = {k: torch.zeros(sd[k].shape, dtype=torch.float32, device=dev) for k in _PARAMS}
+        self._losses = torch.zeros(3, dtype=torch.float64, device=dev)
+        self._g = _abi.BeA2CGrads(*(self.grads[k].data_ptr() for k in _PARAMS), self._losses.data_ptr())
+        self._weights = None
+
+    def _params(self):
+        ps = dict(self.policy.named_parameters())
+        ws = []
+        for k in _PARAMS:
+            w = ps[k].detach()
+            if w.dtype != torch.float32 or not w.is_contiguous() or w.device != self.env.device or \
+                    w.shape != self.grads[k].shape:
+                raise ValueError(f"policy parameter {k} must be a contiguous f32 tensor of the shape A2CGrad was "
+                                 "made for, on the env's device")
+            ws.append(w)
+        return ws
+
+    def __call__(self, obs: torch.Tensor, actions: torch.Tensor, returns_norm: torch.Tensor, valid: torch.Tensor):
+        """obs (T, N, F) or (rows, F) u8; actions u8, returns_norm f32, valid u8 or bool, each (T, N) or
+        (rows,): contiguous, on the env's device.  Asynchronous on the caller's current stream.
+        Returns ``.grads``."""
+        dev, F = self.env.device, self.env.obs_dim
+        if obs.dtype != torch.uint8 or obs.dim() not in (2, 3) or obs.shape[-1] != F or not obs.is_contiguous() or \
+                obs.device != dev:
+            raise ValueError("obs must be a (T, N, F) or (rows, F) contiguous u8 tensor on the env's device")
+        lead = tuple(obs.shape[:-1])
+        if actions.dtype != torch.uint8 or tuple(actions.shape) != lead or not actions.is_contiguous() or \
+                actions.device != dev:
+            raise ValueError("actions must be a contiguous u8 tensor of obs' leading shape on the env's device")
+        if returns_norm.dtype != torch.float32 or tuple(returns_norm.shape) != lead or \
+                not returns_norm.is_contiguous() or returns_norm.device != dev:
+            raise ValueError("returns_norm must be a contiguous f32 tensor of obs' leading shape on the env's device")
+        if valid.dtype not in (torch.bool, torch.uint8) or tuple(valid.shape) != lead or not valid.is_contiguous() or \
+                valid.device != dev:
+            raise ValueError("valid must be a contiguous bool / u8 tensor of obs' leading shape on the env's device")
+        rows = 1
+        for n in lead:
+            rows *= int(n)
+        ws = self._params()
+        w = _abi.BeA2CWeights(*(x.data_ptr() for x in ws), self.hidden, self.num_actions)
+        rc = self._lib.be_a2c_grad(self.env._ctx, obs.data_ptr(), actions.data_ptr(), returns_norm.data_ptr(),
+                                   valid.data_ptr(), rows, C.byref(w), self.workspace.data_ptr(),
+                                   self.workspace.numel() * 8, C.byref(self._g), self.env._stream())
+        if rc:
+            _abi.check(rc, self.env._ctx)
+        self._weights = ws          # keep alive until the kernels have run
+        return self.grads
+
+    def losses(self):
+        """(policy_loss, value_loss, count) of the last call as Python numbers (synchronises)."""
+        pl, vl, n = self._losses.tolist()
+        return pl, vl, int(n)
 
 
 class Rollout:
@@ -302,14 +384,45 @@ def a2c_losses(policy: Policy, obs: torch.Tensor, actions: torch.Tensor, rewards
     return pl, vl
 
 
-def a2c_update(rollout: "Rollout", optimizer, gamma: float = 0.99, targets: str = "torch"):
+def _a2c_update_hip_grads(rollout: "Rollout", optimizer, gamma: float, targets: str) -> float:
+    """a2c_update(grads="hip"): the losses and gradients from ``A2CGrad`` (cached on the rollout)."""
+    T, N = rollout.rewards.shape
+    if targets == "hip":
+        t = rollout.targets(gamma, with_returns=False)
+        Rn, valid = t.returns_norm, t.valid
+    else:
+        Rn, valid = _torch_targets(rollout.rewards, rollout.dones, gamma)
+        Rn, valid = Rn.reshape(T, N).contiguous(), valid.reshape(T, N).contiguous()
+    ag = getattr(rollout, "_a2c_grad", None)
+    if ag is None or ag.policy is not rollout.policy:
+        ag = rollout._a2c_grad = A2CGrad(rollout.env, rollout.policy)
+    grads = ag(rollout.obs[:-1], rollout.actions, Rn, valid)
+    for k, prm in rollout.policy.named_parameters():
+        if prm.grad is None:
+            prm.grad = grads[k].clone()
+        else:
+            prm.grad.copy_(grads[k])
+    pl, vl, _ = ag.losses()
+    optimizer.step()
+    if rollout.hp is not None:
+        rollout.hp.load(rollout.policy)
+    return pl + vl
+
+
+def a2c_update(rollout: "Rollout", optimizer, gamma: float = 0.99, targets: str = "torch", grads: str = "torch"):
     """One A2C step on a recorded rollout (record_obs=True): loss.backward(), optimizer.step(),
     then re-pack the new weights for the HIP policy kernel.  Returns the loss value.
-    targets: "torch" (a2c_losses' own recursion and statistics) or "hip" (``Rollout.targets``)."""
+    targets: "torch" (a2c_losses' own recursion and statistics) or "hip" (``Rollout.targets``).
+    grads: "torch" (a2c_losses + autograd) or "hip" (``A2CGrad``: the losses and every .grad from
+    ``be_a2c_grad``, no autograd graph and no f32 copy of the observations)."""
     if rollout.obs is None:
         raise ValueError("a2c_update needs Rollout(record_obs=True)")
     if targets not in ("torch", "hip"):
         raise ValueError("targets must be 'torch' or 'hip'")
+    if grads not in ("torch", "hip"):
+        raise ValueError("grads must be 'torch' or 'hip'")
+    if grads == "hip":
+        return _a2c_update_hip_grads(rollout, optimizer, gamma, targets)
     tg = None
     if targets == "hip":
         t = rollout.targets(gamma, with_returns=False)

@@ -348,6 +348,55 @@ int be_a2c_targets(be_ctx* ctx, const double* rewards, const uint8_t* dones, con
                    const double* bootstrap, int32_t steps, double gamma, double eps,
                    const be_a2c_out* out, void* stream);
 
+/* ---- A2C losses and gradients: the rest of finish_episode (examples/ball_cnn_ac3.py:233-244) ----
+ * The policy and value losses of Policy(W) over `rows` recorded rows (T*N of any rollout; every
+ * row offset is 64-bit) and their gradients, i.e. what loss.backward() leaves in the six .grad.
+ * Contiguous device arrays: obs (rows, F) u8 with F = 4 + W*W of ctx (bytes 0 and 1, what the step
+ * kernels write), actions (rows) u8, returns_norm (rows) f32 and valid (rows) u8 as be_a2c_targets
+ * writes them.  A row is active when valid != 0 and action < num_actions; any other row adds
+ * nothing.  Per active row, in f32 (x = the row's observation, a = its action, Rn = returns_norm):
+ *   pre = W1 x + b1;  h = max(pre, 0);  z = Wa h + ba;  v = Wv h + bv
+ *   logp = z[a] - logsumexp(z)                       (log-softmax: finite where softmax underflows)
+ *   adv = Rn - v                                     (v not differentiated here: value.item(), :234)
+ *   policy_loss += -logp * adv;                      dz_j = adv * (p_j - [j == a]),  p = softmax(z)
+ *   d = v - Rn;  value_loss += |d| < 1 ? 0.5 d^2 : |d| - 0.5;    dv = |d| < 1 ? d : sign(d)  (:238)
+ *   dh = Wa^T dz + Wv^T dv;  dpre = pre > 0 ? dh : 0
+ *   gW1 += dpre (x) x;  gb1 += dpre;  gWa += dz (x) h;  gba += dz;  gWv += dv h;  gbv += dv
+ * No float atomics: each workgroup of a grid that depends only on rows and the device adds its
+ * rows in a fixed order and writes its sums to `workspace`; a second kernel adds the workgroups'
+ * sums in workgroup order in f64 and rounds once to f32 (the losses stay f64).  Two calls on the
+ * same inputs and device give the same bits whatever the workspace held.  Every output element is
+ * written on every call (zeros when no row is active; rows = 0 is valid).  Asynchronous on
+ * `stream`, no allocation and no synchronisation (graph-capturable).                       */
+typedef struct be_a2c_weights {           /* state_dict layout, as be_policy_load takes them */
+  const float* fc1_weight;          /* (hidden, F)            Policy.fc1, :121 / :137          */
+  const float* fc1_bias;            /* (hidden)                                                */
+  const float* action_head_weight;  /* (num_actions, hidden)  Policy.action_head, :124 / :142  */
+  const float* action_head_bias;    /* (num_actions)                                           */
+  const float* value_head_weight;   /* (1, hidden)            Policy.value_head, :127 / :145   */
+  const float* value_head_bias;     /* (1)                                                     */
+  int32_t hidden;                   /* 1 .. 256 (be_policy_create's bounds; F <= 128)          */
+  int32_t num_actions;              /* 1 .. 15                                                 */
+} be_a2c_weights;
+
+typedef struct be_a2c_grads {             /* what loss.backward() (:243) leaves in each .grad */
+  float* fc1_weight;                /* (hidden, F)                                             */
+  float* fc1_bias;                  /* (hidden)                                                */
+  float* action_head_weight;        /* (num_actions, hidden)                                   */
+  float* action_head_bias;          /* (num_actions)                                           */
+  float* value_head_weight;         /* (1, hidden)                                             */
+  float* value_head_bias;           /* (1)                                                     */
+  double* losses;                   /* [3]: sum of policy losses (:236), sum of value losses
+                                       (:238), number of active rows                           */
+} be_a2c_grads;
+
+/* Bytes of workspace be_a2c_grad needs on ctx's device (8-byte aligned; independent of rows);
+ * < 0: an error code.                                                                       */
+int64_t be_a2c_grad_workspace_bytes(be_ctx* ctx, int32_t hidden, int32_t num_actions);
+int be_a2c_grad(be_ctx* ctx, const uint8_t* obs, const uint8_t* actions, const float* returns_norm,
+                const uint8_t* valid, int64_t rows, const be_a2c_weights* weights, void* workspace,
+                int64_t workspace_bytes, const be_a2c_grads* grads, void* stream);
+
 /* ---- the createBoard physics profile ----
  * N independent ballenv_pygame.createBoard worlds (reset :460-513, step :650-675,
  * calc_reward :680-706) with the 20 featureExtractor features (featureExtractor.py:247-265)
