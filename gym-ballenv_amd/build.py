@@ -8,6 +8,9 @@ object) and linked into one shared library:
                     autoreset pool's fill) and their dispatcher
   csrc/abi.hip      be_ctx and the step engine's C entry points (no kernels; step_types.h is the
                     interface between the two)
+  csrc/internal.h   the host toolkit every unit's entry points share: error reporting, entering a
+  csrc/host_logic.h context's device, the status word (internal.h); the pool's bookkeeping, the blob
+                    layout, be_pool_entry's word order, be_out_at (host_logic.h: no HIP, CPU-tested)
   csrc/policy.hip   select_action kernel (-fno-slp-vectorize: scalar f32 FMAs
                     interleave better with MFMAs than SLP-packed ones on gfx950)
   csrc/features.hip sibling observation formats (prep_state2 block counts)
@@ -42,7 +45,8 @@ VGPR_MFMA = ["-mllvm", "-amdgpu-mfma-vgpr-form"]
 KARG_PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
 UNITS = {"ballenv.hip": [*VGPR_MFMA, *KARG_PRELOAD], "abi.hip": [], "policy.hip": ["-fno-slp-vectorize", *VGPR_MFMA],
          "features.hip": [], "board.hip": [], "a2c.hip": [], "a2c_grad.hip": []}
-HEADERS = [HDR, *(os.path.join(CSRC, h) for h in ("philox.h", "internal.h", "policy_core.h", "diag.h", "step_types.h"))]
+HEADERS = [HDR, *(os.path.join(CSRC, h) for h in ("philox.h", "internal.h", "host_logic.h", "pool_layout.h", "policy_core.h", "diag.h",
+                                              "step_types.h"))]
 
 
 def _stale(out, deps):

@@ -296,9 +296,7 @@ int be_a2c_targets(be_ctx* ctx, const double* rewards, const uint8_t* dones, con
   if (!isfinite(gamma)) return be_ctx_fail(ctx, BE_E_INVALID, "be_a2c_targets: gamma must be finite");
   if (!(eps >= 0.0)) return be_ctx_fail(ctx, BE_E_INVALID, "be_a2c_targets: eps must be >= 0");
   const be_ctx_view cv = be_ctx_get(ctx);
-  const DeviceGuard dg(cv.device);   // the caller's current device is restored on return
-  hipError_t e = dg.err;
-  if (e != hipSuccess) return be_ctx_fail(ctx, BE_E_HIP, hipGetErrorString(e));
+  BE_ENTER_DEVICE(be_ctx_err(ctx), cv.device);
   AParams p{rewards, dones, values, bootstrap, out->returns, out->returns_norm, out->advantage, out->valid,
             cv.num_envs, steps, gamma, eps};
   const dim3 grid((unsigned)((cv.num_envs + 63) / 64)), block(64);
@@ -310,9 +308,7 @@ int be_a2c_targets(be_ctx* ctx, const double* rewards, const uint8_t* dones, con
     if (out->advantage) hipLaunchKernelGGL((a2c_targets_kernel<false, true>), grid, block, 0, hs, p);
     else hipLaunchKernelGGL((a2c_targets_kernel<false, false>), grid, block, 0, hs, p);
   }
-  e = hipGetLastError();
-  if (e != hipSuccess) return be_ctx_fail(ctx, BE_E_HIP, hipGetErrorString(e));
-  return BE_OK;
+  return be_launched(be_ctx_err(ctx));
 }
 
 }  // extern "C"

@@ -476,9 +476,7 @@ int be_a2c_grad(be_ctx* ctx, const uint8_t* obs, const uint8_t* actions, const f
   if (workspace_bytes < (int64_t)slots * L.slot_bytes)
     return be_ctx_fail(ctx, BE_E_INVALID, "be_a2c_grad: workspace is smaller than be_a2c_grad_workspace_bytes");
   if (L.lds > 160 * 1024) return be_ctx_fail(ctx, BE_E_INVALID, "be_a2c_grad: the tile exceeds the LDS budget");
-  const DeviceGuard dg(cv.device);   // the caller's current device is restored on return
-  hipError_t e = dg.err;
-  if (e != hipSuccess) return be_ctx_fail(ctx, BE_E_HIP, hipGetErrorString(e));
+  BE_ENTER_DEVICE(be_ctx_err(ctx), cv.device);
   const int64_t ntiles = (rows + R - 1) / R;
   const int grid = (int)(ntiles < 1 ? 1 : (ntiles < slots ? ntiles : slots));
   GParams p{obs, actions, returns_norm, valid, w->fc1_weight, w->fc1_bias, w->action_head_weight,
@@ -493,14 +491,11 @@ int be_a2c_grad(be_ctx* ctx, const uint8_t* obs, const uint8_t* actions, const f
     hipLaunchKernelGGL((a2c_grad_kernel<INST_W10.MT, INST_W10.FTM, INST_W10.KT1, true>), gd, bd, (size_t)L.lds, hs, p);
   else
     hipLaunchKernelGGL((a2c_grad_kernel<INST_ANY.MT, INST_ANY.FTM, INST_ANY.KT1, false>), gd, bd, (size_t)L.lds, hs, p);
-  e = hipGetLastError();
-  if (e != hipSuccess) return be_ctx_fail(ctx, BE_E_HIP, hipGetErrorString(e));
+  if (int rc = be_launched(be_ctx_err(ctx))) return rc;
   RParams r{(const uint8_t*)workspace, grid, L, g->fc1_weight, g->fc1_bias, g->action_head_weight,
             g->action_head_bias, g->value_head_weight, g->value_head_bias, g->losses};
   hipLaunchKernelGGL(a2c_grad_reduce, dim3((unsigned)((L.P + 3 + 255) / 256)), dim3(256), 0, hs, r);
-  e = hipGetLastError();
-  if (e != hipSuccess) return be_ctx_fail(ctx, BE_E_HIP, hipGetErrorString(e));
-  return BE_OK;
+  return be_launched(be_ctx_err(ctx));
 }
 
 }  // extern "C"

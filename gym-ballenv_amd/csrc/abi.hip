@@ -15,17 +15,19 @@
 #include <string.h>
 
 #include "ballenv.h"
+#include "host_logic.h"
 #include "internal.h"
 #include "step_types.h"
 
 using namespace bestep;
+using namespace behost;
 
 struct be_ctx {
   be_config cfg;
   TablesX tables;
   KParams base;      // config-derived part of every launch's KParams
   int device;
-  int* status;
+  StatusWord status;
   TablesX* d_tables;
   bool generic_only;   // BALLENV_GENERIC_KERNELS=1: never use the fixed-shape step kernels (A/B diagnostics)
   bool unit_moves;     // every action move in {-1,0,1}^2 (fixed-shape kernels' packed table)
@@ -37,13 +39,11 @@ struct be_ctx {
   Launch step_launch[2];   // be_step's kernel without / with the fixed-shape preconditions (fixed per context)
   Launch step_launch_pool; // the fixed-shape kernel's pool variant (when the context has a pool)
   int64_t blob_hdr[8]; // be_save_state's header (host memory that outlives the async copy)
-  // the autoreset pool (layout in step_types.h): allocated when be_step's fixed-shape kernel consumes it
+  // the autoreset pool (layout in pool_layout.h): allocated when be_step's fixed-shape kernel consumes it
   uint32_t* pool;      // nullptr: no pool (every reset inline)
   int64_t pool_bytes;
   Launch pool_fill;    // the pool's fill kernel for this window
-  int pool_period;     // be_step queues a fill every pool_period step launches (0: only be_reset / be_load_state / be_pool_fill)
-  int pool_calls;      // step launches since the last fill
-  const void* pool_owner;   // the state (its episode array) the pool serves: other states step without it
+  PoolBook book;       // the pool's owner state, and when be_step queues a fill
   mutable struct { KFn fn; int lds; bool ok; } lds_cache[4];   // fits_lds() answers per (kernel, dynamic LDS)
   mutable std::mutex lds_mu;                                    // guards lds_cache (const entries may race)
   char err[512];
@@ -82,19 +82,8 @@ static void env_lanes(const char* name, std::initializer_list<int> allowed, int&
 
 static thread_local char g_err[512];
 
-static int fail(be_ctx* ctx, int code, const char* fmt, const char* detail) {
-  char* dst = ctx ? ctx->err : g_err;
-  snprintf(dst, 512, fmt, detail ? detail : "");
-  return code;
-}
-
-#define HIP_TRY(ctx, expr)                                                                     \
-  do {                                                                                         \
-    hipError_t e_ = (expr);                                                                    \
-    if (e_ != hipSuccess) return fail(ctx, BE_E_HIP, "HIP error: %s", hipGetErrorString(e_)); \
-  } while (0)
-
 // library-internal accessors for the other translation units (csrc/internal.h)
+char* be_ctx_err(be_ctx* ctx) { return ctx ? ctx->err : g_err; }
 be_ctx_view be_ctx_get(const be_ctx* ctx) {
   be_ctx_view v;
   v.num_envs = ctx->cfg.num_envs; v.window = ctx->cfg.window; v.device = ctx->device;
@@ -102,16 +91,23 @@ be_ctx_view be_ctx_get(const be_ctx* ctx) {
   v.env_offset = ctx->cfg.env_offset;
   return v;
 }
-int be_ctx_fail(be_ctx* ctx, int code, const char* msg) { return fail(ctx, code, "%s", msg); }
-static int check_state(be_ctx* ctx, const be_state* st);
-int be_ctx_check_state(be_ctx* ctx, const be_state* st) { return check_state(ctx, st); }
+int be_ctx_check_state(be_ctx* ctx, const be_state* st) {
+  if (!ctx) return be_ctx_fail(nullptr, BE_E_INVALID, "ctx is NULL");
+  if (!st || !st->agent || !st->goal || !st->prev_dist || !st->total_dist || !st->ep_return || !st->ep_len ||
+      !st->episode)
+    return be_ctx_fail(ctx, BE_E_INVALID, "be_state has a NULL pointer");
+  if (ctx->cfg.num_static > 0 && !st->static_obs) return be_ctx_fail(ctx, BE_E_INVALID, "static_obs is NULL");
+  if (ctx->cfg.num_dynamic > 0 && (!st->dyn_obs || !st->dyn_goal))
+    return be_ctx_fail(ctx, BE_E_INVALID, "dyn_obs/dyn_goal is NULL");
+  return BE_OK;
+}
 
 extern "C" {
 
 int be_abi_version(void) { return BE_ABI_VERSION; }
 
 int be_config_default(be_config* c, int32_t num_envs, int32_t window) {
-  if (!c) return fail(nullptr, BE_E_INVALID, "%s", "cfg is NULL");
+  if (!c) return be_ctx_fail(nullptr, BE_E_INVALID, "cfg is NULL");
   memset(c, 0, sizeof(*c));
   c->num_envs = num_envs; c->window = window; c->env_offset = 0; c->seed = 0xBA11ull;
   c->screen_width = 500; c->screen_height = 500;                                     // ballenv_env.py:11-18
@@ -192,7 +188,7 @@ int be_config_check(const be_config* c, char* msg, int32_t msg_len) {
   return BE_OK;
 bad:
   if (msg && msg_len > 0) snprintf(msg, (size_t)msg_len, "%s", buf);
-  return fail(nullptr, BE_E_INVALID, "invalid config: %s", buf);
+  return be_fail(g_err, BE_E_INVALID, "invalid config: %s", buf);
 }
 
 // Can a reset re-sample the agent (ballenv_env.py:121-126, quirk Q9)?  Only if some agent spawn
@@ -248,13 +244,21 @@ int64_t be_stats_slots(const be_config* c) {
   return ((int64_t)c->num_envs + 31) / 32;
 }
 
+// Frees what a context holds on its device, and the context (the caller has entered the device).
+static void ctx_release(be_ctx* ctx) {
+  ctx->status.release();
+  if (ctx->d_tables) (void)hipFree(ctx->d_tables);
+  if (ctx->pool) (void)hipFree(ctx->pool);
+  delete ctx;
+}
+
 int be_create(const be_config* cfg, int32_t device, be_ctx** out) {
-  if (!out) return fail(nullptr, BE_E_INVALID, "%s", "out is NULL");
+  if (!out) return be_ctx_fail(nullptr, BE_E_INVALID, "out is NULL");
   *out = nullptr;
   char msg[256];
-  if (be_config_check(cfg, msg, sizeof msg) != BE_OK) return fail(nullptr, BE_E_INVALID, "invalid config: %s", msg);
+  if (be_config_check(cfg, msg, sizeof msg) != BE_OK) return be_fail(g_err, BE_E_INVALID, "invalid config: %s", msg);
   be_ctx* ctx = new (std::nothrow) be_ctx();
-  if (!ctx) return fail(nullptr, BE_E_NOMEM, "%s", "out of host memory");
+  if (!ctx) return be_ctx_fail(nullptr, BE_E_NOMEM, "out of host memory");
   ctx->cfg = *cfg;
   ctx->device = device;
   KParams& b = ctx->base;
@@ -348,8 +352,7 @@ int be_create(const be_config* cfg, int32_t device, be_ctx** out) {
   }
   const DeviceGuard dg(device);   // the caller's current device is restored on return
   hipError_t e = dg.err;
-  if (e == hipSuccess) e = hipMalloc(&ctx->status, sizeof(int));
-  if (e == hipSuccess) e = hipMemset(ctx->status, 0, sizeof(int));
+  if (e == hipSuccess) e = ctx->status.create();
   if (e == hipSuccess) e = hipMalloc(&ctx->d_tables, sizeof(TablesX));
   if (e == hipSuccess) e = hipMemcpy(ctx->d_tables, &ctx->tables, sizeof(TablesX), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipDeviceSynchronize();
@@ -365,26 +368,19 @@ int be_create(const be_config* cfg, int32_t device, be_ctx** out) {
     // 13.71-13.72 (profiles/r06_onelane_pool_ab.txt)
     const bool consumes = fixed_ok(ctx) && cfg->autoreset && fixed.consumes_pool &&
                           (fixed.kind != KIND_FIXED1 || (int64_t)cfg->num_envs <= onelane_max);
-    bool want = consumes && (int64_t)cfg->num_envs <= POOL_MAX_ENVS;
-    if (const char* v = getenv("BALLENV_POOL")) want = want && strcmp(v, "0") != 0;   // A/B: "0" = no pool
-    ctx->pool_period = 128;
-    if (const char* v = getenv("BALLENV_POOL_PERIOD")) ctx->pool_period = std::max(0, atoi(v));
+    const bool want = consumes && (int64_t)cfg->num_envs <= POOL_MAX_ENVS && PoolBook::env_enabled();
+    ctx->book.period_from_env();
     if (want && e == hipSuccess) {
       ctx->pool_bytes = pool_bytes_per_env(FIX_NS, FIX_ND) * cfg->num_envs;
       ctx->pool_fill = pick_pool_fill(cfg->window);
-      e = hipMalloc(&ctx->pool, (size_t)ctx->pool_bytes);
-      if (e == hipSuccess) e = hipMemset(ctx->pool, 0, (size_t)ctx->pool_bytes);   // every entry unwritten
-      if (e == hipSuccess) e = hipDeviceSynchronize();
+      e = be_pool_alloc(&ctx->pool, ctx->pool_bytes);
+      ctx->book.has = e == hipSuccess;
       ctx->step_launch_pool = pick_kernel(ctx->cfg, MODE_STEP, true, ctx->step_lanes, ctx->step5_lpe, true);
     }
   }
   if (e != hipSuccess) {
-    int rc = fail(nullptr, BE_E_HIP, "HIP error in be_create: %s", hipGetErrorString(e));
-    if (ctx->status) (void)hipFree(ctx->status);
-    if (ctx->d_tables) (void)hipFree(ctx->d_tables);
-    if (ctx->pool) (void)hipFree(ctx->pool);
-    delete ctx;
-    return rc;
+    ctx_release(ctx);
+    return be_fail(g_err, BE_E_HIP, "HIP error in be_create: %s", hipGetErrorString(e));
   }
   *out = ctx;
   return BE_OK;
@@ -393,20 +389,7 @@ int be_create(const be_config* cfg, int32_t device, be_ctx** out) {
 int be_destroy(be_ctx* ctx) {
   if (!ctx) return BE_OK;
   const DeviceGuard dg(ctx->device);   // the caller's current device is restored on return
-  if (ctx->status) (void)hipFree(ctx->status);
-  if (ctx->d_tables) (void)hipFree(ctx->d_tables);
-  if (ctx->pool) (void)hipFree(ctx->pool);
-  delete ctx;
-  return BE_OK;
-}
-
-static int check_state(be_ctx* ctx, const be_state* st) {
-  if (!st || !st->agent || !st->goal || !st->prev_dist || !st->total_dist || !st->ep_return || !st->ep_len ||
-      !st->episode)
-    return fail(ctx, BE_E_INVALID, "%s", "be_state has a NULL pointer");
-  if (ctx->cfg.num_static > 0 && !st->static_obs) return fail(ctx, BE_E_INVALID, "%s", "static_obs is NULL");
-  if (ctx->cfg.num_dynamic > 0 && (!st->dyn_obs || !st->dyn_goal))
-    return fail(ctx, BE_E_INVALID, "%s", "dyn_obs/dyn_goal is NULL");
+  ctx_release(ctx);
   return BE_OK;
 }
 
@@ -422,7 +405,7 @@ static KParams make_params(be_ctx* ctx, const be_state* st, const be_out* out) {
     a.final_len = out->final_len; a.stats = out->stats;
   }
   a.tables = &ctx->d_tables->t;
-  a.status = ctx->status;
+  a.status = ctx->status.word;
   return a;
 }
 
@@ -432,26 +415,21 @@ static void obs_only(KParams& a) {
   a.final_return = nullptr; a.final_len = nullptr; a.stats = nullptr;
 }
 
-// The pool's fill over every env of the state (the caller holds the DeviceGuard)
+// The pool's fill over every env of the state (its caller has claimed the pool or found the fill due)
 static void launch_pool_fill(be_ctx* ctx, const KParams& a, void* stream) {
   KParams f = a;
   f.pool = ctx->pool;
   launch_kernel(ctx->pool_fill, f, (hipStream_t)stream);
-  ctx->pool_calls = 0;
 }
 
-// steps > 1 (be_step_n): `steps` launches of the same kernel, actions advancing by N per step.
+// The launches of one entry point, which has entered the context's device.  steps > 1 (be_step_n):
+// `steps` launches of the same kernel, actions advancing by N per step.
 static int launch(be_ctx* ctx, int mode, KParams& a, void* stream, int32_t steps = 1) {
   const bool fixed = mode == MODE_STEP && a.tape == nullptr && a.actions != nullptr && fixed_ok(ctx);
   if (((uintptr_t)a.obs & 15) || ((uintptr_t)a.obs_f32 & 15))
-    return fail(ctx, BE_E_INVALID, "%s", "obs / obs_f32 must be 16-byte aligned");
-  const DeviceGuard dg(ctx->device);   // the caller's current device is restored on return
-  HIP_TRY(ctx, dg.err);
-  // the pool serves one state (its owner: the state last reset / loaded, else the first one stepped);
-  // a step of any other state draws its resets inline, so a context's entries are only ever written
-  // and read by the launches of one state, which the caller orders on its stream anyway
-  if (ctx->pool && fixed && !ctx->pool_owner) ctx->pool_owner = a.episode;
-  const bool use_pool = ctx->pool && fixed && a.episode == ctx->pool_owner;
+    return be_ctx_fail(ctx, BE_E_INVALID, "obs / obs_f32 must be 16-byte aligned");
+  // the pool serves one state (PoolBook, host_logic.h): a step of any other state draws its resets inline
+  const bool use_pool = fixed && ctx->book.step(a.episode);
   a.pool = use_pool ? ctx->pool : nullptr;
   const Launch L = mode == MODE_STEP ? (use_pool ? ctx->step_launch_pool : ctx->step_launch[fixed ? 1 : 0])
                                      : pick_kernel(ctx->cfg, mode);
@@ -459,94 +437,80 @@ static int launch(be_ctx* ctx, int mode, KParams& a, void* stream, int32_t steps
   for (int32_t s = 0; s < steps; ++s) {
     launch_kernel(L, a, (hipStream_t)stream);
     a.actions += N;
-    if (use_pool && ctx->pool_period > 0 && ++ctx->pool_calls >= ctx->pool_period) launch_pool_fill(ctx, a, stream);
+    if (use_pool && ctx->book.fill_due()) launch_pool_fill(ctx, a, stream);
   }
-  HIP_TRY(ctx, hipGetLastError());
-  return BE_OK;
+  return be_launched(ctx->err);
+}
+
+// be_reset, be_load_state, be_pool_fill: st becomes the pool's state, with its next two episodes per env drawn
+static int claim_and_fill(be_ctx* ctx, const be_state* st, void* stream) {
+  if (!ctx->pool) return BE_OK;
+  ctx->book.claim(st->episode);
+  launch_pool_fill(ctx, make_params(ctx, st, nullptr), stream);
+  return be_launched(ctx->err);
 }
 
 int be_reset(be_ctx* ctx, const be_state* st, const uint8_t* mask, const int16_t* reset_tape, int32_t tape_len,
              const be_out* out, void* stream) {
-  if (!ctx) return fail(nullptr, BE_E_INVALID, "%s", "ctx is NULL");
-  if (int rc = check_state(ctx, st)) return rc;
-  if (reset_tape && tape_len < 0) return fail(ctx, BE_E_INVALID, "%s", "tape_len < 0");
-  if (!out || (!out->obs && !out->obs_f32)) return fail(ctx, BE_E_INVALID, "%s", "be_reset needs out->obs or out->obs_f32");
+  if (int rc = be_ctx_check_state(ctx, st)) return rc;
+  if (reset_tape && tape_len < 0) return be_ctx_fail(ctx, BE_E_INVALID, "tape_len < 0");
+  if (!out || (!out->obs && !out->obs_f32)) return be_ctx_fail(ctx, BE_E_INVALID, "be_reset needs out->obs or out->obs_f32");
   KParams a = make_params(ctx, st, out);
   obs_only(a);
   a.mask = mask; a.reset_tape = reset_tape; a.reset_tape_len = reset_tape ? tape_len : 0;
+  BE_ENTER_DEVICE(ctx->err, ctx->device);
   if (int rc = launch(ctx, MODE_RESET, a, stream)) return rc;
-  if (ctx->pool) {   // this state's next two episodes per env, ahead of its first step
-    ctx->pool_owner = st->episode;
-    const DeviceGuard dg(ctx->device);
-    HIP_TRY(ctx, dg.err);
-    launch_pool_fill(ctx, a, stream);
-    HIP_TRY(ctx, hipGetLastError());
-  }
-  return BE_OK;
+  return claim_and_fill(ctx, st, stream);   // ahead of this state's first step
 }
 
 int be_step(be_ctx* ctx, const be_state* st, const uint8_t* actions, const int16_t* action_deltas,
             const int16_t* draw_tape, const be_out* out, void* stream) {
-  if (!ctx) return fail(nullptr, BE_E_INVALID, "%s", "ctx is NULL");
-  if (int rc = check_state(ctx, st)) return rc;
-  if (!out || !out->reward || !out->done) return fail(ctx, BE_E_INVALID, "%s", "be_step needs out->reward and out->done");
-  if (draw_tape && ctx->cfg.autoreset) return fail(ctx, BE_E_INVALID, "%s", "draw tapes (parity mode) need autoreset = 0");
+  if (int rc = be_ctx_check_state(ctx, st)) return rc;
+  if (!out || !out->reward || !out->done) return be_ctx_fail(ctx, BE_E_INVALID, "be_step needs out->reward and out->done");
+  if (draw_tape && ctx->cfg.autoreset) return be_ctx_fail(ctx, BE_E_INVALID, "draw tapes (parity mode) need autoreset = 0");
   KParams a = make_params(ctx, st, out);
   a.actions = actions; a.deltas = action_deltas; a.tape = draw_tape;
+  BE_ENTER_DEVICE(ctx->err, ctx->device);
   return launch(ctx, MODE_STEP, a, stream);
 }
 
 int be_step_n(be_ctx* ctx, const be_state* st, const uint8_t* actions, int32_t steps, const be_out* out,
               void* stream) {
-  if (!ctx) return fail(nullptr, BE_E_INVALID, "%s", "ctx is NULL");
-  if (int rc = check_state(ctx, st)) return rc;
-  if (!actions || steps < 0) return fail(ctx, BE_E_INVALID, "%s", "be_step_n needs actions and steps >= 0");
-  if (!out || !out->reward || !out->done) return fail(ctx, BE_E_INVALID, "%s", "be_step_n needs out->reward and out->done");
+  if (int rc = be_ctx_check_state(ctx, st)) return rc;
+  if (!actions || steps < 0) return be_ctx_fail(ctx, BE_E_INVALID, "be_step_n needs actions and steps >= 0");
+  if (!out || !out->reward || !out->done) return be_ctx_fail(ctx, BE_E_INVALID, "be_step_n needs out->reward and out->done");
   if (steps == 0) return BE_OK;
   KParams a = make_params(ctx, st, out);
   a.actions = actions;
+  BE_ENTER_DEVICE(ctx->err, ctx->device);
   return launch(ctx, MODE_STEP, a, stream, steps);
 }
 
 int be_rollout(be_ctx* ctx, const be_state* st, const uint8_t* actions, int32_t steps, const be_out* out,
                void* stream) {
-  if (!ctx) return fail(nullptr, BE_E_INVALID, "%s", "ctx is NULL");
-  if (int rc = check_state(ctx, st)) return rc;
-  if (!actions || steps < 0) return fail(ctx, BE_E_INVALID, "%s", "be_rollout needs actions and steps >= 0");
+  if (int rc = be_ctx_check_state(ctx, st)) return rc;
+  if (!actions || steps < 0) return be_ctx_fail(ctx, BE_E_INVALID, "be_rollout needs actions and steps >= 0");
   if (!out || !out->obs || !out->reward || !out->done)
-    return fail(ctx, BE_E_INVALID, "%s", "be_rollout needs out->obs, out->reward and out->done");
-  if (out->obs_f32) return fail(ctx, BE_E_INVALID, "%s", "be_rollout writes u8 obs only (obs_f32 must be NULL)");
+    return be_ctx_fail(ctx, BE_E_INVALID, "be_rollout needs out->obs, out->reward and out->done");
+  if (out->obs_f32) return be_ctx_fail(ctx, BE_E_INVALID, "be_rollout writes u8 obs only (obs_f32 must be NULL)");
   const int64_t N = ctx->cfg.num_envs, F = 4 + (int64_t)ctx->cfg.window * ctx->cfg.window;
   if (((uintptr_t)out->obs & 15) || (N * F) % 16)
-    return fail(ctx, BE_E_INVALID, "%s", "be_rollout needs a 16-byte aligned obs and num_envs * (4+W*W) % 16 == 0");
+    return be_ctx_fail(ctx, BE_E_INVALID, "be_rollout needs a 16-byte aligned obs and num_envs * (4+W*W) % 16 == 0");
   if (steps == 0) return BE_OK;
   const Launch L = pick_rollout(ctx->cfg, fixed_ok(ctx), ctx->roll5_lpe);
-  bool fused = false;
-  {   // every HIP query (fits_lds' function attributes) on the context's device
-    const DeviceGuard dg(ctx->device);   // the caller's current device is restored on return
-    HIP_TRY(ctx, dg.err);
-    fused = fits_lds(ctx, L);
-  }
-  if (fused) {
+  BE_ENTER_DEVICE(ctx->err, ctx->device);   // (fits_lds queries the function's attributes on the context's device)
+  if (fits_lds(ctx, L)) {
     KParams a = make_params(ctx, st, out);
     a.actions = actions; a.steps = steps;
-    const DeviceGuard dg(ctx->device);   // the caller's current device is restored on return
-    HIP_TRY(ctx, dg.err);
     launch_kernel(L, a, (hipStream_t)stream);
-    HIP_TRY(ctx, hipGetLastError());
-    return BE_OK;
+    return be_launched(ctx->err);
   }
-  // any other config: one be_step per step into the (steps, N, ...) slices (same results)
+  // any other config: one step launch per step into the (steps, N, ...) slices (same results)
   for (int32_t s = 0; s < steps; ++s) {
-    be_out o = *out;
-    o.obs = out->obs + s * N * F;
-    o.reward = out->reward + s * N;
-    o.done = out->done + s * N;
-    if (o.truncated) o.truncated = out->truncated + s * N;
-    if (o.terminal_obs) o.terminal_obs = out->terminal_obs + s * N * F;
-    if (o.final_return) o.final_return = out->final_return + s * N;
-    if (o.final_len) o.final_len = out->final_len + s * N;
-    if (int rc = be_step(ctx, st, actions + s * N, nullptr, nullptr, &o, stream)) return rc;
+    const be_out o = be_out_at(*out, s, N, F);
+    KParams a = make_params(ctx, st, &o);
+    a.actions = actions + s * N;
+    if (int rc = launch(ctx, MODE_STEP, a, stream)) return rc;
   }
   return BE_OK;
 }
@@ -555,8 +519,6 @@ int be_rollout(be_ctx* ctx, const be_state* st, const uint8_t* actions, int32_t 
 
 int be_internal_policy_rollout(be_ctx* ctx, const be_state* st, const be_pol_rollout_args* r, void* stream) {
   const Launch L = pick_policy_rollout(ctx->cfg, fixed_ok(ctx), r->HT, r->KS, r->NO);
-  const DeviceGuard dg(ctx->device);   // the caller's current device is restored on return; every
-  HIP_TRY(ctx, dg.err);                // HIP query below (fits_lds) runs on the context's device
   if (!fits_lds(ctx, L)) return 0;   // the caller loops select_action + be_step instead
   KParams a = make_params(ctx, st, r->out);
   a.steps = r->steps;
@@ -564,184 +526,129 @@ int be_internal_policy_rollout(be_ctx* ctx, const be_state* st, const be_pol_rol
   a.obs_in = r->obs_in; a.obs_last = r->obs_last;
   a.act_out = r->act->action; a.logp_out = r->act->log_prob; a.value_out = r->act->value;
   launch_kernel(L, a, (hipStream_t)stream);
-  HIP_TRY(ctx, hipGetLastError());
-  return 1;
+  const int rc = be_launched(ctx->err);
+  return rc ? rc : 1;
 }
 
 extern "C" {
 
 int be_observe(be_ctx* ctx, const be_state* st, const be_out* out, void* stream) {
-  if (!ctx) return fail(nullptr, BE_E_INVALID, "%s", "ctx is NULL");
-  if (int rc = check_state(ctx, st)) return rc;
-  if (!out || (!out->obs && !out->obs_f32)) return fail(ctx, BE_E_INVALID, "%s", "be_observe needs out->obs or out->obs_f32");
+  if (int rc = be_ctx_check_state(ctx, st)) return rc;
+  if (!out || (!out->obs && !out->obs_f32)) return be_ctx_fail(ctx, BE_E_INVALID, "be_observe needs out->obs or out->obs_f32");
   KParams a = make_params(ctx, st, out);
   obs_only(a);
+  BE_ENTER_DEVICE(ctx->err, ctx->device);
   return launch(ctx, MODE_OBSERVE, a, stream);
 }
 
 int be_sample_actions(be_ctx* ctx, uint8_t* actions_out, int32_t steps, uint64_t seed, void* stream) {
-  if (!ctx || !actions_out || steps < 0) return fail(ctx, BE_E_INVALID, "%s", "bad arguments to be_sample_actions");
+  if (!ctx || !actions_out || steps < 0) return be_ctx_fail(ctx, BE_E_INVALID, "bad arguments to be_sample_actions");
   if (steps == 0) return BE_OK;
-  const DeviceGuard dg(ctx->device);   // the caller's current device is restored on return
-  HIP_TRY(ctx, dg.err);
+  BE_ENTER_DEVICE(ctx->err, ctx->device);
   launch_sample_actions(actions_out, ctx->cfg.num_envs, steps, ctx->cfg.env_offset, ctx->cfg.num_actions,
                         (unsigned long long)seed, (hipStream_t)stream);
-  HIP_TRY(ctx, hipGetLastError());
-  return BE_OK;
+  return be_launched(ctx->err);
 }
 
-// ---- env-state checkpoint: header + the be_state arrays at 16-byte aligned offsets
-struct BlobLayout { int64_t off[10], bytes[10], total; };
-static BlobLayout blob_layout(const be_config* c) {
-  BlobLayout b;
-  const int64_t N = c->num_envs, ns = c->num_static, nd = c->num_dynamic;
-  const int64_t sz[10] = {4 * N, 4 * N, 8 * N, 8 * N, 8 * N, 4 * N, 4 * N, 4 * ns * N, 4 * nd * N, nd * N};
-  int64_t o = 64;
-  for (int k = 0; k < 10; ++k) { b.off[k] = o; b.bytes[k] = sz[k]; o += (sz[k] + 15) & ~15ll; }
-  b.total = o;
-  return b;
-}
-static void blob_header(const be_config* c, int64_t total, int64_t (&hdr)[8]) {
-  memset(hdr, 0, sizeof hdr);
-  memcpy(&hdr[0], "BALLENV1", 8);
-  hdr[1] = BE_ABI_VERSION; hdr[2] = c->num_envs; hdr[3] = c->num_static; hdr[4] = c->num_dynamic; hdr[5] = total;
-}
-static void state_ptrs(const be_state* st, void* (&p)[10]) {
-  p[0] = st->agent; p[1] = st->goal; p[2] = st->prev_dist; p[3] = st->total_dist; p[4] = st->ep_return;
-  p[5] = st->ep_len; p[6] = st->episode; p[7] = st->static_obs; p[8] = st->dyn_obs; p[9] = st->dyn_goal;
-}
-
+// ---- env-state checkpoint (the blob's layout and header: host_logic.h)
 int64_t be_state_blob_bytes(const be_config* cfg) {
   if (!cfg || cfg->num_envs < 1) return 0;
   return blob_layout(cfg).total;
 }
 
 int be_save_state(be_ctx* ctx, const be_state* st, void* blob, void* stream) {
-  if (!ctx) return fail(nullptr, BE_E_INVALID, "%s", "ctx is NULL");
-  if (int rc = check_state(ctx, st)) return rc;
-  if (!blob) return fail(ctx, BE_E_INVALID, "%s", "blob is NULL");
-  const DeviceGuard dg(ctx->device);   // the caller's current device is restored on return
-  HIP_TRY(ctx, dg.err);
+  if (int rc = be_ctx_check_state(ctx, st)) return rc;
+  if (!blob) return be_ctx_fail(ctx, BE_E_INVALID, "blob is NULL");
+  BE_ENTER_DEVICE(ctx->err, ctx->device);
   const BlobLayout L = blob_layout(&ctx->cfg);
   blob_header(&ctx->cfg, L.total, ctx->blob_hdr);   // lives in the context: safe for an async copy
   hipStream_t s = (hipStream_t)stream;
-  HIP_TRY(ctx, hipMemcpyAsync(blob, ctx->blob_hdr, sizeof ctx->blob_hdr, hipMemcpyDefault, s));
+  BE_HIP_TRY(ctx->err, hipMemcpyAsync(blob, ctx->blob_hdr, sizeof ctx->blob_hdr, hipMemcpyDefault, s));
   void* src[10];
   state_ptrs(st, src);
   for (int k = 0; k < 10; ++k)
     if (L.bytes[k] > 0)
-      HIP_TRY(ctx, hipMemcpyAsync(static_cast<char*>(blob) + L.off[k], src[k], (size_t)L.bytes[k], hipMemcpyDefault, s));
+      BE_HIP_TRY(ctx->err, hipMemcpyAsync(static_cast<char*>(blob) + L.off[k], src[k], (size_t)L.bytes[k], hipMemcpyDefault, s));
   return BE_OK;
 }
 
 int be_load_state(be_ctx* ctx, const be_state* st, const void* blob, void* stream) {
-  if (!ctx) return fail(nullptr, BE_E_INVALID, "%s", "ctx is NULL");
-  if (int rc = check_state(ctx, st)) return rc;
-  if (!blob) return fail(ctx, BE_E_INVALID, "%s", "blob is NULL");
-  const DeviceGuard dg(ctx->device);   // the caller's current device is restored on return
-  HIP_TRY(ctx, dg.err);
+  if (int rc = be_ctx_check_state(ctx, st)) return rc;
+  if (!blob) return be_ctx_fail(ctx, BE_E_INVALID, "blob is NULL");
+  BE_ENTER_DEVICE(ctx->err, ctx->device);
   const BlobLayout L = blob_layout(&ctx->cfg);
   hipStream_t s = (hipStream_t)stream;
   int64_t got[8], want[8];
-  HIP_TRY(ctx, hipMemcpyAsync(got, blob, sizeof got, hipMemcpyDefault, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
+  BE_HIP_TRY(ctx->err, hipMemcpyAsync(got, blob, sizeof got, hipMemcpyDefault, s));
+  BE_HIP_TRY(ctx->err, hipStreamSynchronize(s));
   blob_header(&ctx->cfg, L.total, want);
   if (memcmp(got, want, sizeof got) != 0)
-    return fail(ctx, BE_E_INVALID, "%s", "state blob header does not match this context (magic, ABI, N, Ns, Nd)");
+    return be_ctx_fail(ctx, BE_E_INVALID, "state blob header does not match this context (magic, ABI, N, Ns, Nd)");
   void* dst[10];
   state_ptrs(st, dst);
   for (int k = 0; k < 10; ++k)
     if (L.bytes[k] > 0)
-      HIP_TRY(ctx, hipMemcpyAsync(dst[k], static_cast<const char*>(blob) + L.off[k], (size_t)L.bytes[k], hipMemcpyDefault, s));
-  if (ctx->pool) {   // the loaded episodes' next entries (the pool's entries need no invalidation:
-                     // each is a pure function of (seed, global id, episode) and is checked by its tag)
-    ctx->pool_owner = st->episode;
-    launch_pool_fill(ctx, make_params(ctx, st, nullptr), stream);
-    HIP_TRY(ctx, hipGetLastError());
-  }
-  return BE_OK;
+      BE_HIP_TRY(ctx->err, hipMemcpyAsync(dst[k], static_cast<const char*>(blob) + L.off[k], (size_t)L.bytes[k], hipMemcpyDefault, s));
+  // the loaded episodes' next entries (the pool's entries need no invalidation: each is a pure
+  // function of (seed, global id, episode) and is checked by its tag)
+  return claim_and_fill(ctx, st, stream);
 }
 
 int be_pool_fill(be_ctx* ctx, const be_state* st, void* stream) {
-  if (!ctx) return fail(nullptr, BE_E_INVALID, "%s", "ctx is NULL");
-  if (int rc = check_state(ctx, st)) return rc;
+  if (int rc = be_ctx_check_state(ctx, st)) return rc;
   if (!ctx->pool) return BE_OK;
-  const DeviceGuard dg(ctx->device);
-  HIP_TRY(ctx, dg.err);
-  ctx->pool_owner = st->episode;
-  launch_pool_fill(ctx, make_params(ctx, st, nullptr), stream);
-  HIP_TRY(ctx, hipGetLastError());
-  return BE_OK;
+  BE_ENTER_DEVICE(ctx->err, ctx->device);
+  return claim_and_fill(ctx, st, stream);
 }
 
 int be_pool_invalidate(be_ctx* ctx, void* stream) {
-  if (!ctx) return fail(nullptr, BE_E_INVALID, "%s", "ctx is NULL");
+  if (!ctx) return be_ctx_fail(nullptr, BE_E_INVALID, "ctx is NULL");
   if (!ctx->pool) return BE_OK;
-  const DeviceGuard dg(ctx->device);
-  HIP_TRY(ctx, dg.err);
-  HIP_TRY(ctx, hipMemsetAsync(ctx->pool, 0, (size_t)ctx->pool_bytes, (hipStream_t)stream));
+  BE_ENTER_DEVICE(ctx->err, ctx->device);
+  BE_HIP_TRY(ctx->err, hipMemsetAsync(ctx->pool, 0, (size_t)ctx->pool_bytes, (hipStream_t)stream));
   return BE_OK;
 }
 
 int be_pool_set_period(be_ctx* ctx, int32_t period) {
-  if (!ctx) return fail(nullptr, BE_E_INVALID, "%s", "ctx is NULL");
-  if (period < 0) return fail(ctx, BE_E_INVALID, "%s", "pool period must be >= 0");
-  ctx->pool_period = period;
-  ctx->pool_calls = 0;
+  if (!ctx) return be_ctx_fail(nullptr, BE_E_INVALID, "ctx is NULL");
+  if (period < 0) return be_ctx_fail(ctx, BE_E_INVALID, "pool period must be >= 0");
+  ctx->book.set_period(period);
   return BE_OK;
 }
 
 int64_t be_pool_bytes(const be_ctx* ctx) { return ctx && ctx->pool ? ctx->pool_bytes : 0; }
 
-int32_t be_pool_period(const be_ctx* ctx) { return ctx ? ctx->pool_period : 0; }
+int32_t be_pool_period(const be_ctx* ctx) { return ctx ? ctx->book.period : 0; }
 
 int be_pool_entry(be_ctx* ctx, int32_t env, int32_t slot, uint32_t* words, double* f64, int32_t write) {
-  if (!ctx) return fail(nullptr, BE_E_INVALID, "%s", "ctx is NULL");
-  if (!ctx->pool) return fail(ctx, BE_E_INVALID, "%s", "this context has no autoreset pool");
+  if (!ctx) return be_ctx_fail(nullptr, BE_E_INVALID, "ctx is NULL");
+  if (!ctx->pool) return be_ctx_fail(ctx, BE_E_INVALID, "this context has no autoreset pool");
   if (env < 0 || env >= ctx->cfg.num_envs || slot < 0 || slot > 1 || !words || !f64)
-    return fail(ctx, BE_E_INVALID, "%s", "bad arguments to be_pool_entry");
-  const DeviceGuard dg(ctx->device);
-  HIP_TRY(ctx, dg.err);
-  HIP_TRY(ctx, hipDeviceSynchronize());
-  // the header's word order (TAG, AGENT, GOAL, ROWS0 | flags << 30, ROWS1, ROWS2, obstacles) from / to
-  // the tags array and the entry body
+    return be_ctx_fail(ctx, BE_E_INVALID, "bad arguments to be_pool_entry");
+  BE_ENTER_DEVICE(ctx->err, ctx->device);
+  BE_HIP_TRY(ctx->err, hipDeviceSynchronize());
+  // the entry's tag and body (pool_layout.h) from / to the header's word order (host_logic.h)
   const int64_t n = ctx->cfg.num_envs, x = (int64_t)slot * n + env;
   constexpr int NBW = pool_body_words(FIX_NS, FIX_ND), NO = FIX_NS + FIX_ND;
   char* tv = reinterpret_cast<char*>(ctx->pool) + x * 8;
   char* body = reinterpret_cast<char*>(ctx->pool) + 16 * n + x * 4 * NBW;
   uint32_t t[2], b[NBW];
-  HIP_TRY(ctx, hipMemcpy(t, tv, sizeof t, hipMemcpyDeviceToHost));
-  HIP_TRY(ctx, hipMemcpy(b, body, sizeof b, hipMemcpyDeviceToHost));
+  BE_HIP_TRY(ctx->err, hipMemcpy(t, tv, sizeof t, hipMemcpyDeviceToHost));
+  BE_HIP_TRY(ctx->err, hipMemcpy(b, body, sizeof b, hipMemcpyDeviceToHost));
   if (!write) {
-    words[0] = t[0]; words[1] = b[PB_AGENT]; words[2] = b[PB_GOAL];
-    words[3] = (b[PB_ROWS] & 0x3FFFFFFFu) | ((t[1] & 3u) << 30);
-    words[4] = b[PB_ROWS + 1]; words[5] = b[PB_ROWS + 2];
-    for (int k = 0; k < NO; ++k) words[6 + k] = b[PB_OBS + k];
-    memcpy(&f64[0], &b[PB_PREV], 8);
-    memcpy(&f64[1], &b[PB_TOTAL], 8);
+    pool_entry_unpack(t, b, NO, words, f64);
     return BE_OK;
   }
-  t[0] = words[0]; t[1] = (words[3] >> 30) & 3u;
-  b[PB_AGENT] = words[1]; b[PB_GOAL] = words[2];
-  b[PB_ROWS] = words[3] & 0x3FFFFFFFu; b[PB_ROWS + 1] = words[4]; b[PB_ROWS + 2] = words[5];
-  for (int k = 0; k < NO; ++k) b[PB_OBS + k] = words[6 + k];
-  memcpy(&b[PB_PREV], &f64[0], 8);
-  memcpy(&b[PB_TOTAL], &f64[1], 8);
-  HIP_TRY(ctx, hipMemcpy(tv, t, sizeof t, hipMemcpyHostToDevice));
-  HIP_TRY(ctx, hipMemcpy(body, b, sizeof b, hipMemcpyHostToDevice));
+  pool_entry_pack(words, f64, NO, t, b);
+  BE_HIP_TRY(ctx->err, hipMemcpy(tv, t, sizeof t, hipMemcpyHostToDevice));
+  BE_HIP_TRY(ctx->err, hipMemcpy(body, b, sizeof b, hipMemcpyHostToDevice));
   return BE_OK;
 }
 
 int be_status(be_ctx* ctx, int32_t* status_out, void* stream) {
-  if (!ctx || !status_out) return fail(ctx, BE_E_INVALID, "%s", "bad arguments to be_status");
-  const DeviceGuard dg(ctx->device);   // the caller's current device is restored on return
-  HIP_TRY(ctx, dg.err);
-  HIP_TRY(ctx, hipStreamSynchronize((hipStream_t)stream));
-  int v = 0;
-  HIP_TRY(ctx, hipMemcpy(&v, ctx->status, sizeof v, hipMemcpyDeviceToHost));
-  const int zero = 0;
-  HIP_TRY(ctx, hipMemcpy(ctx->status, &zero, sizeof zero, hipMemcpyHostToDevice));
-  *status_out = v;
+  if (!ctx || !status_out) return be_ctx_fail(ctx, BE_E_INVALID, "bad arguments to be_status");
+  BE_ENTER_DEVICE(ctx->err, ctx->device);
+  BE_HIP_TRY(ctx->err, ctx->status.take(stream, status_out));
   return BE_OK;
 }
 

@@ -687,32 +687,9 @@ __device__ __forceinline__ int dyn_move(const KParams& p, const Tables& t, int& 
 
 // Philox-mode dyn_move for the fixed-shape kernels, written as straight-line integer code so
 // the scheduler can interleave the obstacles (select by mask, no divergent regions).
-// Returns the goal index after the step; (ox, oy) is moved unless change.
-__device__ __forceinline__ int dyn_move_philox(const KParams& p, const Tables& t, int& ox, int& oy, int gi, int speed,
-                                               bool change, uint32_t f, uint32_t& flags) {
-  const int32_t gp = t.goal[gi];
-  const int n_other = t.n_other[gi];
-  const int tx = px(gp) - ox, ty = py(gp) - oy;
-  const bool both = (tx != 0) & (ty != 0);
-  const uint32_t p1 = __umul24(f, 100u);
-  const uint32_t src = both ? (p1 & 0xFFFFFFu) : f;
-  const uint32_t m2 = 2u * (__umul24(src, 9u) >> 24);            // 2 * OBS_MOVES index
-  const bool directed = both & ((int)(p1 >> 24) < p.certainty);
-  const int sx = (tx > 0) - (tx < 0), sy = (ty > 0) - (ty < 0);
-  const int rx = (int)((OBS_MX >> m2) & 3u) - 1, ry = (int)((OBS_MY >> m2) & 3u) - 1;
-  const int mx = directed ? sx : rx, my = directed ? sy : ry;
-  const int step = change ? 0 : speed;                             // goal change: no move (Q5)
-  const int nx = ox + mx * step, ny = oy + my * step;
-  const int pick = (int)(__umul24(f, (uint32_t)n_other) >> 24);
-  const int ng = t.other[gi][min(pick, BE_MAX_GOALS - 1)];
-  flags |= (change && n_other == 0) ? (uint32_t)BE_STATUS_NO_GOAL : 0u;
-  flags |= ((uint32_t)(nx + 32768) > 65535u || (uint32_t)(ny + 32768) > 65535u) ? (uint32_t)BE_STATUS_COORD_RANGE : 0u;
-  ox = nx; oy = ny;
-  return (change && n_other > 0) ? ng : gi;
-}
-
-// dyn_move_philox for pairwise-distinct goals (the fixed-shape kernels): newGoalList(g) is
-// every other goal in order, so the pick needs no table; n_other = num_goals - 1 >= 1.
+// Returns the goal index after the step; (ox, oy) is moved unless change.  The kernels' goals are
+// pairwise distinct, so newGoalList(g) is every other goal in order and the pick needs no table;
+// n_other = num_goals - 1 >= 1.
 __device__ __forceinline__ int dyn_move_fixed(const KParams& p, const Tables& t, int& ox, int& oy, int gi, int speed,
                                               bool change, uint32_t f, uint32_t& flags) {
   const int32_t gp = t.goal[gi];

@@ -37,7 +37,6 @@
 // that needs more: every rejection loop becomes one ballot over 64 candidate attempts).
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <math.h>
 #include <new>
 #include <stdint.h>
@@ -46,6 +45,7 @@
 #include <string.h>
 
 #include "ballenv.h"
+#include "host_logic.h"
 #include "internal.h"
 #include "philox.h"
 
@@ -873,26 +873,25 @@ struct be_board {
   be_board_config cfg;
   int device;
   bool lpe2;           // BALLENV_BOARD_LPE=2: two lanes per env (A/B)
-  int* status;
+  StatusWord status;
   BoardTables* d_tables;
   uint32_t* pool;      // the autoreset pool (Philox autoreset, one lane per env), or nullptr
   int64_t pool_bytes;
-  int pool_period, pool_calls;
-  const void* pool_owner;   // the state (its episode array) the pool serves
+  behost::PoolBook book;   // the pool's owner state, and when be_board_step queues a fill
   char err[512];
 };
 
 static thread_local char g_board_err[512];
 
-static int bfail(be_board* b, int code, const char* msg) {
-  snprintf(b ? b->err : g_board_err, 512, "%s", msg);
-  return code;
-}
+static char* board_err(be_board* b) { return b ? b->err : g_board_err; }
+static int bfail(be_board* b, int code, const char* msg) { return be_fail(board_err(b), code, "%s", msg); }
 
-static int bhip(be_board* b, hipError_t e) {
-  char buf[256];
-  snprintf(buf, sizeof buf, "HIP error: %s", hipGetErrorString(e));
-  return bfail(b, BE_E_HIP, buf);
+// Frees what a board holds on its device, and the board (the caller has entered the device).
+static void board_release(be_board* b) {
+  b->status.release();
+  if (b->d_tables) (void)hipFree(b->d_tables);
+  if (b->pool) (void)hipFree(b->pool);
+  delete b;
 }
 
 extern "C" {
@@ -936,29 +935,20 @@ int be_board_create(const be_board_config* cfg, int32_t device, be_board** out) 
   for (int a = 0; a < cfg->num_actions; ++a) { t.actions[a][0] = cfg->actions[a][0]; t.actions[a][1] = cfg->actions[a][1]; }
   const DeviceGuard dg(device);   // the caller's current device is restored on return
   hipError_t e = dg.err;
-  if (e == hipSuccess) e = hipMalloc(&b->status, sizeof(int));
-  if (e == hipSuccess) e = hipMemset(b->status, 0, sizeof(int));
+  if (e == hipSuccess) e = b->status.create();
   if (e == hipSuccess) e = hipMalloc(&b->d_tables, sizeof t);
   if (e == hipSuccess) e = hipMemcpy(b->d_tables, &t, sizeof t, hipMemcpyHostToDevice);
-  {  // the autoreset pool: Philox autoreset, one lane per env (BALLENV_POOL=0 disables it, A/B)
-    bool want = cfg->autoreset && !b->lpe2 && (int64_t)cfg->num_envs <= BPOOL_MAX_ENVS;
-    if (const char* v = getenv("BALLENV_POOL")) want = want && strcmp(v, "0") != 0;
-    b->pool_period = 128;
-    if (const char* v = getenv("BALLENV_POOL_PERIOD")) b->pool_period = std::max(0, atoi(v));
-    if (want && e == hipSuccess) {
-      b->pool_bytes = 2ll * cfg->num_envs * (8 + 4ll * bpool_words(cfg->num_static));
-      e = hipMalloc(&b->pool, (size_t)b->pool_bytes);
-      if (e == hipSuccess) e = hipMemset(b->pool, 0, (size_t)b->pool_bytes);   // every entry unwritten
-      if (e == hipSuccess) e = hipDeviceSynchronize();
-    }
+  // the autoreset pool: Philox autoreset, one lane per env (BALLENV_POOL=0 disables it, A/B)
+  const bool want = cfg->autoreset && !b->lpe2 && (int64_t)cfg->num_envs <= BPOOL_MAX_ENVS && behost::PoolBook::env_enabled();
+  b->book.period_from_env();
+  if (want && e == hipSuccess) {
+    b->pool_bytes = 2ll * cfg->num_envs * (8 + 4ll * bpool_words(cfg->num_static));
+    e = be_pool_alloc(&b->pool, b->pool_bytes);
+    b->book.has = e == hipSuccess;
   }
   if (e != hipSuccess) {
-    const int rc = bhip(nullptr, e);
-    if (b->status) (void)hipFree(b->status);
-    if (b->d_tables) (void)hipFree(b->d_tables);
-    if (b->pool) (void)hipFree(b->pool);
-    delete b;
-    return rc;
+    board_release(b);
+    return be_hip_fail(g_board_err, e);
   }
   *out = b;
   return BE_OK;
@@ -967,10 +957,7 @@ int be_board_create(const be_board_config* cfg, int32_t device, be_board** out) 
 int be_board_destroy(be_board* b) {
   if (!b) return BE_OK;
   const DeviceGuard dg(b->device);   // the caller's current device is restored on return
-  if (b->status) (void)hipFree(b->status);
-  if (b->d_tables) (void)hipFree(b->d_tables);
-  if (b->pool) (void)hipFree(b->pool);
-  delete b;
+  board_release(b);
   return BE_OK;
 }
 
@@ -994,9 +981,7 @@ static int board_launch(be_board* b, const be_board_state* st, const be_board_ou
   if (mode == 3 && steps == 0) return BE_OK;
   if (mode == 2 && !out->features) return bfail(b, BE_E_INVALID, "be_board_observe needs out->features");
   if (tape && tape_len < 0) return bfail(b, BE_E_INVALID, "tape_len < 0");
-  const DeviceGuard dg(b->device);   // the caller's current device is restored on return
-  hipError_t e = dg.err;
-  if (e != hipSuccess) return bhip(b, e);
+  BE_ENTER_DEVICE(b->err, b->device);
   const be_board_config& c = b->cfg;
   BParams p;
   memset(&p, 0, sizeof p);
@@ -1004,7 +989,7 @@ static int board_launch(be_board* b, const be_board_state* st, const be_board_ou
   p.ep_len = st->ep_len; p.episode = st->episode; p.statics = st->static_obs;
   p.features = out->features; p.reward = out->reward; p.done = out->done; p.truncated = out->truncated;
   p.actions = actions; p.deltas = deltas; p.mask = mask; p.tape = tape; p.tape_len = tape ? tape_len : 0;
-  p.tables = b->d_tables; p.status = b->status; p.seed = c.seed;
+  p.tables = b->d_tables; p.status = b->status.word; p.seed = c.seed;
   p.n = c.num_envs; p.ns = c.num_static; p.num_actions = c.num_actions; p.time_limit = c.time_limit;
   p.autoreset = c.autoreset; p.gid0 = (int32_t)(uint32_t)c.env_offset; p.mode = mode; p.steps = steps;
   p.W = c.screen_width; p.H = c.screen_height; p.sox = c.strip_obs_x; p.soy = c.strip_obs_y;
@@ -1017,10 +1002,9 @@ static int board_launch(be_board* b, const be_board_state* st, const be_board_ou
   // and 4.96 vs 3.97 us fused at 65 536 envs -- the per-env f64 chains (acos, hypot, the reward
   // divide) run on both lanes and outweigh the halved obstacle terms (profiles/r03_board_lanes_ab.txt)
   const int lpe = (tape || !b->lpe2) ? 1 : 2;
-  // the pool serves one state (the one last reset, else the first one stepped): its steps run the
-  // pool instance, any other state's steps draw every reset inline
-  if (b->pool && mode == 0 && !b->pool_owner) b->pool_owner = st->episode;
-  const bool use_pool = b->pool && mode == 0 && lpe == 1 && st->episode == b->pool_owner;
+  // the pool serves one state (PoolBook, host_logic.h; a board with a pool runs one lane per env): its
+  // steps run the pool instance, any other state's steps draw every reset inline
+  const bool use_pool = mode == 0 && b->book.step(st->episode);
   p.pool = use_pool ? b->pool : nullptr;
   void (*fn)(BParams) = nullptr;
 #define BE_BOARD_PICK(R, LL, ...)                                                                                       \
@@ -1034,22 +1018,16 @@ static int board_launch(be_board* b, const be_board_state* st, const be_board_ou
   const int epb = 256 / lpe;
   hipLaunchKernelGGL(fn, dim3((unsigned)((c.num_envs + epb - 1) / epb)), dim3(256), 0, (hipStream_t)stream, p);
   // the pool's fill: after a reset (its state's next two episodes), and every pool period of steps
-  const bool fill = b->pool && (mode == 1 || (use_pool && b->pool_period > 0 && ++b->pool_calls >= b->pool_period));
-  if (fill) {
-    if (mode == 1) b->pool_owner = st->episode;
-    if (st->episode == b->pool_owner) {
-      b->pool_calls = 0;
-      BParams f = p;
-      f.pool = b->pool; f.tape = nullptr; f.tape_len = 0;
-      void (*ff)(BParams) = c.num_static <= 4 ? board_pool_fill<4> : c.num_static <= 6 ? board_pool_fill<6>
-                          : c.num_static <= 8 ? board_pool_fill<8> : c.num_static <= 12 ? board_pool_fill<12>
-                          : c.num_static <= 16 ? board_pool_fill<16> : board_pool_fill<32>;
-      hipLaunchKernelGGL(ff, dim3((unsigned)((c.num_envs + 255) / 256)), dim3(256), 0, (hipStream_t)stream, f);
-    }
+  if (b->pool && mode == 1) b->book.claim(st->episode);
+  if ((b->pool && mode == 1) || (use_pool && b->book.fill_due())) {
+    BParams f = p;
+    f.pool = b->pool; f.tape = nullptr; f.tape_len = 0;
+    void (*ff)(BParams) = c.num_static <= 4 ? board_pool_fill<4> : c.num_static <= 6 ? board_pool_fill<6>
+                        : c.num_static <= 8 ? board_pool_fill<8> : c.num_static <= 12 ? board_pool_fill<12>
+                        : c.num_static <= 16 ? board_pool_fill<16> : board_pool_fill<32>;
+    hipLaunchKernelGGL(ff, dim3((unsigned)((c.num_envs + 255) / 256)), dim3(256), 0, (hipStream_t)stream, f);
   }
-  e = hipGetLastError();
-  if (e != hipSuccess) return bhip(b, e);
-  return BE_OK;
+  return be_launched(b->err);
 }
 
 int be_board_reset(be_board* b, const be_board_state* st, const uint8_t* mask, const double* reset_tape,
@@ -1075,15 +1053,8 @@ BE_DIAG_BOARD_ENTRIES   // diagnostics builds only (diag.h)
 
 int be_board_status(be_board* b, int32_t* status_out, void* stream) {
   if (!b || !status_out) return bfail(b, BE_E_INVALID, "bad arguments to be_board_status");
-  const DeviceGuard dg(b->device);   // the caller's current device is restored on return
-  hipError_t e = dg.err;
-  if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-  int v = 0;
-  if (e == hipSuccess) e = hipMemcpy(&v, b->status, sizeof v, hipMemcpyDeviceToHost);
-  const int zero = 0;
-  if (e == hipSuccess) e = hipMemcpy(b->status, &zero, sizeof zero, hipMemcpyHostToDevice);
-  if (e != hipSuccess) return bhip(b, e);
-  *status_out = v;
+  BE_ENTER_DEVICE(b->err, b->device);
+  BE_HIP_TRY(b->err, b->status.take(stream, status_out));
   return BE_OK;
 }
 

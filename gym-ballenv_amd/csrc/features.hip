@@ -140,19 +140,14 @@ __global__ __launch_bounds__(256) void blocks_kernel(BParams p) {
 extern "C" {
 
 int be_observe_blocks(be_ctx* ctx, const be_state* st, uint8_t* out, float* out_f32, void* stream) {
-  if (!ctx) return be_ctx_fail(nullptr, BE_E_INVALID, "ctx is NULL");
   if (int rc = be_ctx_check_state(ctx, st)) return rc;
   if (!out && !out_f32) return be_ctx_fail(ctx, BE_E_INVALID, "be_observe_blocks needs out or out_f32");
   const be_ctx_view cv = be_ctx_get(ctx);
-  const DeviceGuard dg(cv.device);   // the caller's current device is restored on return
-  hipError_t e = dg.err;
-  if (e != hipSuccess) return be_ctx_fail(ctx, BE_E_HIP, hipGetErrorString(e));
+  BE_ENTER_DEVICE(be_ctx_err(ctx), cv.device);
   BParams p{st->agent, st->goal, st->static_obs, st->dyn_obs, out, out_f32, cv.num_envs, cv.num_static, cv.num_dynamic};
   const size_t lds = 4 * (size_t)(out_f32 ? BLK_WAVE_F32 : BLK_WAVE_U8);
   hipLaunchKernelGGL(blocks_kernel, dim3((unsigned)((cv.num_envs + 255) / 256)), dim3(256), lds, (hipStream_t)stream, p);
-  e = hipGetLastError();
-  if (e != hipSuccess) return be_ctx_fail(ctx, BE_E_HIP, hipGetErrorString(e));
-  return BE_OK;
+  return be_launched(be_ctx_err(ctx));
 }
 
 }  // extern "C"

@@ -1,0 +1,110 @@
+// host_logic.h -- the host side's logic that needs no HIP: the autoreset pool's bookkeeping, the
+// checkpoint blob's layout, be_pool_entry's word order and the per-step slice of a be_out.  Only
+// ballenv.h, pool_layout.h and standard headers, so the host C++ compiler alone builds and tests it
+// (tests/host_logic_main.cpp); internal.h is the half that touches HIP.
+#pragma once
+#include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "ballenv.h"
+#include "pool_layout.h"
+
+namespace behost {
+
+// The autoreset pool's bookkeeping, for the step engine's context and the board's alike (the device
+// memory is the context's own).  The pool serves one state, its owner, named by the state's episode
+// array: the state last reset / loaded / filled for, else the first one stepped.  A step of any
+// other state draws its resets inline.
+struct PoolBook {
+  bool has = false;            // the context allocated a pool (false: every method answers "no pool")
+  int period = 128;            // owner step launches per fill (0: explicit fills only)
+  int calls = 0;               // owner step launches since the last fill
+  const void* owner = nullptr;
+
+  // BALLENV_POOL: "0" disables the pool (A/B).  BALLENV_POOL_PERIOD: the period, clamped at 0.
+  static bool env_enabled() { const char* v = getenv("BALLENV_POOL"); return !v || strcmp(v, "0") != 0; }
+  void period_from_env() {
+    const char* v = getenv("BALLENV_POOL_PERIOD");
+    const int n = v ? atoi(v) : 128;
+    period = n > 0 ? n : 0;
+  }
+  // A step launch of `state` that meets the pool's preconditions: does it use the pool?  Claims an
+  // unowned pool.  (An ownership change is not ordered against the previous owner's launches here:
+  // the caller orders them, include/ballenv.h.)
+  bool step(const void* state) {
+    if (!has) return false;
+    if (!owner) owner = state;
+    return state == owner;
+  }
+  // One step launch of the owner went out: is a fill due now?  A due fill restarts the count.
+  bool fill_due() {
+    if (period <= 0 || ++calls < period) return false;
+    calls = 0;
+    return true;
+  }
+  // A reset, a load or an explicit fill for `state`: it becomes the owner, and the fill that
+  // follows restarts the count.
+  void claim(const void* state) { owner = state; calls = 0; }
+  void set_period(int p) { period = p; calls = 0; }
+};
+
+// ---- env-state checkpoint: a 64-byte header + the be_state arrays at 16-byte aligned offsets
+struct BlobLayout { int64_t off[10], bytes[10], total; };
+inline BlobLayout blob_layout(const be_config* c) {
+  BlobLayout b;
+  const int64_t N = c->num_envs, ns = c->num_static, nd = c->num_dynamic;
+  const int64_t sz[10] = {4 * N, 4 * N, 8 * N, 8 * N, 8 * N, 4 * N, 4 * N, 4 * ns * N, 4 * nd * N, nd * N};
+  int64_t o = 64;
+  for (int k = 0; k < 10; ++k) { b.off[k] = o; b.bytes[k] = sz[k]; o += (sz[k] + 15) & ~15ll; }
+  b.total = o;
+  return b;
+}
+inline void blob_header(const be_config* c, int64_t total, int64_t (&hdr)[8]) {
+  memset(hdr, 0, sizeof hdr);
+  memcpy(&hdr[0], "BALLENV1", 8);
+  hdr[1] = BE_ABI_VERSION; hdr[2] = c->num_envs; hdr[3] = c->num_static; hdr[4] = c->num_dynamic; hdr[5] = total;
+}
+inline void state_ptrs(const be_state* st, void* (&p)[10]) {
+  p[0] = st->agent; p[1] = st->goal; p[2] = st->prev_dist; p[3] = st->total_dist; p[4] = st->ep_return;
+  p[5] = st->ep_len; p[6] = st->episode; p[7] = st->static_obs; p[8] = st->dyn_obs; p[9] = st->dyn_goal;
+}
+
+// ---- be_pool_entry's word order (TAG, AGENT, GOAL, ROWS0 | flags << 30, ROWS1, ROWS2, the n_obs
+// obstacles; f64: PREV, TOTAL) from / to an entry's (tag, body) pair of pool_layout.h
+inline void pool_entry_unpack(const uint32_t (&tag)[2], const uint32_t* body, int n_obs, uint32_t* words, double* f64) {
+  using namespace bestep;
+  words[0] = tag[0]; words[1] = body[PB_AGENT]; words[2] = body[PB_GOAL];
+  words[3] = (body[PB_ROWS] & 0x3FFFFFFFu) | ((tag[1] & 3u) << 30);
+  words[4] = body[PB_ROWS + 1]; words[5] = body[PB_ROWS + 2];
+  for (int k = 0; k < n_obs; ++k) words[6 + k] = body[PB_OBS + k];
+  memcpy(&f64[0], &body[PB_PREV], 8);
+  memcpy(&f64[1], &body[PB_TOTAL], 8);
+}
+// (writes the words it names; the body's other words keep what they held)
+inline void pool_entry_pack(const uint32_t* words, const double* f64, int n_obs, uint32_t (&tag)[2], uint32_t* body) {
+  using namespace bestep;
+  tag[0] = words[0]; tag[1] = (words[3] >> 30) & 3u;
+  body[PB_AGENT] = words[1]; body[PB_GOAL] = words[2];
+  body[PB_ROWS] = words[3] & 0x3FFFFFFFu; body[PB_ROWS + 1] = words[4]; body[PB_ROWS + 2] = words[5];
+  for (int k = 0; k < n_obs; ++k) body[PB_OBS + k] = words[6 + k];
+  memcpy(&body[PB_PREV], &f64[0], 8);
+  memcpy(&body[PB_TOTAL], &f64[1], 8);
+}
+
+// Step s's slice of a (steps, N, ...) be_out, F = 4 + W*W; NULL members stay NULL and stats, which
+// accumulates over the steps, stays whole.
+inline be_out be_out_at(const be_out& out, int64_t s, int64_t N, int64_t F) {
+  be_out o = out;
+  if (o.obs) o.obs += s * N * F;
+  if (o.obs_f32) o.obs_f32 += s * N * F;
+  if (o.reward) o.reward += s * N;
+  if (o.done) o.done += s * N;
+  if (o.truncated) o.truncated += s * N;
+  if (o.terminal_obs) o.terminal_obs += s * N * F;
+  if (o.final_return) o.final_return += s * N;
+  if (o.final_len) o.final_len += s * N;
+  return o;
+}
+
+}  // namespace behost

@@ -1,7 +1,10 @@
 // internal.h -- library-internal interface between the translation units of
-// libballenv.so (not part of the C ABI in include/ballenv.h).
+// libballenv.so (not part of the C ABI in include/ballenv.h), and the HIP-touching half of the
+// host toolkit every unit's entry points share: error reporting, entering a context's device, the
+// status word.  (The half without HIP: host_logic.h.)
 #pragma once
 #include <stdint.h>
+#include <stdio.h>
 
 #include <hip/hip_runtime.h>
 
@@ -27,14 +30,63 @@ struct DeviceGuard {
   DeviceGuard& operator=(const DeviceGuard&) = delete;
 };
 
+// Error reporting.  `err` is the 512-byte buffer the caller's last-error function reads: the
+// context's, the board's, or the matching thread-local one for a NULL context.  Returns code.
+inline int be_fail(char* err, int code, const char* fmt, const char* detail) {
+  snprintf(err, 512, fmt, detail ? detail : "");
+  return code;
+}
+inline int be_hip_fail(char* err, hipError_t e) { return be_fail(err, BE_E_HIP, "HIP error: %s", hipGetErrorString(e)); }
+#define BE_HIP_TRY(err, expr)                                  \
+  do {                                                         \
+    const hipError_t e_ = (expr);                              \
+    if (e_ != hipSuccess) return be_hip_fail(err, e_);         \
+  } while (0)
+// An entry point's frame: BE_ENTER_DEVICE once, ahead of its first HIP call (the caller's current
+// device is restored when the scope ends), then its launches, then `return be_launched(err)`.
+#define BE_ENTER_DEVICE(errbuf, device)    \
+  const DeviceGuard device_guard_(device); \
+  BE_HIP_TRY(errbuf, device_guard_.err)
+inline int be_launched(char* err) {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? BE_OK : be_hip_fail(err, e);
+}
+
+// The device status word of a context (be_status / be_board_status); the caller holds the device.
+struct StatusWord {
+  int* word = nullptr;
+  hipError_t create() {
+    const hipError_t e = hipMalloc(&word, sizeof(int));
+    return e == hipSuccess ? hipMemset(word, 0, sizeof(int)) : e;
+  }
+  void release() { if (word) (void)hipFree(word); word = nullptr; }
+  // synchronise the stream, then read and clear the word (*out is written on success only)
+  hipError_t take(void* stream, int32_t* out) {
+    hipError_t e = hipStreamSynchronize((hipStream_t)stream);
+    int v = 0;
+    if (e == hipSuccess) e = hipMemcpy(&v, word, sizeof v, hipMemcpyDeviceToHost);
+    const int zero = 0;
+    if (e == hipSuccess) e = hipMemcpy(word, &zero, sizeof zero, hipMemcpyHostToDevice);
+    if (e == hipSuccess) *out = v;
+    return e;
+  }
+};
+// A context's autoreset pool: `bytes` of device memory, every entry unwritten.
+inline hipError_t be_pool_alloc(uint32_t** pool, int64_t bytes) {
+  hipError_t e = hipMalloc(pool, (size_t)bytes);
+  if (e == hipSuccess) e = hipMemset(*pool, 0, (size_t)bytes);
+  return e == hipSuccess ? hipDeviceSynchronize() : e;
+}
+
 struct be_ctx_view {
   int32_t num_envs, window, device, num_static, num_dynamic;
   int64_t env_offset;
 };
 __attribute__((visibility("hidden"))) be_ctx_view be_ctx_get(const be_ctx* ctx);
-// record msg as ctx's last error (or the process-wide one for a NULL ctx); returns code
-__attribute__((visibility("hidden"))) int be_ctx_fail(be_ctx* ctx, int code, const char* msg);
-// be_state pointer checks shared by the entry points (BE_OK or a be_ctx_fail code)
+// ctx's last-error buffer (the calling thread's own for a NULL ctx), and msg recorded in it; returns code
+__attribute__((visibility("hidden"))) char* be_ctx_err(be_ctx* ctx);
+inline int be_ctx_fail(be_ctx* ctx, int code, const char* msg) { return be_fail(be_ctx_err(ctx), code, "%s", msg); }
+// an entry point's ctx and be_state pointer checks ("ctx is NULL" first; BE_OK or a be_ctx_fail code)
 __attribute__((visibility("hidden"))) int be_ctx_check_state(be_ctx* ctx, const be_state* st);
 
 // fused config-5 rollout (be_policy_rollout -> rollout_kernel with the policy in the loop)
@@ -48,6 +100,7 @@ struct be_pol_rollout_args {
   const be_out* out;           // per-step (steps, N, ...) outputs
   const be_act_out* act;       // (steps, N) action / log_prob / value
 };
-// 1: launched; 0: no fused kernel for this env / policy shape (the caller loops); < 0: error
+// 1: launched; 0: no fused kernel for this env / policy shape (the caller loops); < 0: error.
+// The caller has entered the context's device.
 __attribute__((visibility("hidden"))) int be_internal_policy_rollout(be_ctx* ctx, const be_state* st,
                                                                      const be_pol_rollout_args* a, void* stream);

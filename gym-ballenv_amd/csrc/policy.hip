@@ -46,6 +46,7 @@
 #include <string.h>
 
 #include "ballenv.h"
+#include "host_logic.h"
 #include "internal.h"
 #include "philox.h"
 #include "policy_core.h"
@@ -246,19 +247,6 @@ PolKernel pick_policy(int H, int F, int A) {
 
 }  // namespace
 
-#define POL_TRY(ctx, expr)                                  \
-  do {                                                      \
-    hipError_t e_ = (expr);                                 \
-    if (e_ != hipSuccess) return pol_hip_fail(ctx, e_);     \
-  } while (0)
-
-static int pol_hip_fail(be_ctx* ctx, hipError_t e) {
-  char buf[256];
-  snprintf(buf, sizeof buf, "HIP error: %s", hipGetErrorString(e));
-  return be_ctx_fail(ctx, BE_E_HIP, buf);
-}
-
-
 struct be_policy {
   be_ctx* ctx;
   be_ctx_view cv;
@@ -271,6 +259,14 @@ struct be_policy {
   bool loaded;
   int dbg;
 };
+
+// Frees what a policy holds on its device, and the policy (the caller has entered the device).
+static void policy_release(be_policy* pol) {
+  if (pol->img) (void)hipFree(pol->img);
+  if (pol->obs4) (void)hipFree(pol->obs4);
+  if (pol->zero4) (void)hipFree(pol->zero4);
+  delete pol;
+}
 
 extern "C" {
 
@@ -298,26 +294,21 @@ int be_policy_create(be_ctx* ctx, int32_t hidden, int32_t num_actions, be_policy
     return be_ctx_fail(ctx, BE_E_INVALID, "packed policy exceeds the LDS budget");
   }
   const DeviceGuard dg(cv.device);   // the caller's current device is restored on return
-  int rc = dg.err == hipSuccess ? BE_OK : pol_hip_fail(ctx, dg.err);
-  hipError_t e = hipSuccess;
-  if (rc == BE_OK) e = hipMalloc(&pol->img, (size_t)pol->L.total);
-  if (rc == BE_OK && e == hipSuccess) e = hipMemset(pol->img, 0, (size_t)pol->L.total);
-  if (rc == BE_OK && e == hipSuccess) e = hipMalloc(&pol->obs4, (size_t)4 * F);
-  if (rc == BE_OK && e == hipSuccess) e = hipMalloc(&pol->zero4, 4 * sizeof(uint32_t));
-  if (rc == BE_OK && e == hipSuccess) e = hipMemset(pol->zero4, 0, 4 * sizeof(uint32_t));
-  if (rc == BE_OK && e == hipSuccess) {
+  hipError_t e = dg.err;
+  if (e == hipSuccess) e = hipMalloc(&pol->img, (size_t)pol->L.total);
+  if (e == hipSuccess) e = hipMemset(pol->img, 0, (size_t)pol->L.total);
+  if (e == hipSuccess) e = hipMalloc(&pol->obs4, (size_t)4 * F);
+  if (e == hipSuccess) e = hipMalloc(&pol->zero4, 4 * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMemset(pol->zero4, 0, 4 * sizeof(uint32_t));
+  if (e == hipSuccess) {
     uint8_t h[4 * POL_MAXF];
     memset(h, 0, sizeof h);
     for (int q = 0; q < 4; ++q) h[q * F + q] = 1;
     e = hipMemcpy(pol->obs4, h, (size_t)4 * F, hipMemcpyHostToDevice);
   }
-  if (rc == BE_OK && e != hipSuccess) rc = pol_hip_fail(ctx, e);
-  if (rc != BE_OK) {
-    if (pol->img) (void)hipFree(pol->img);
-    if (pol->obs4) (void)hipFree(pol->obs4);
-    if (pol->zero4) (void)hipFree(pol->zero4);
-    delete pol;
-    return rc;
+  if (e != hipSuccess) {
+    policy_release(pol);
+    return be_hip_fail(be_ctx_err(ctx), e);
   }
   *out = pol;
   return BE_OK;
@@ -326,10 +317,7 @@ int be_policy_create(be_ctx* ctx, int32_t hidden, int32_t num_actions, be_policy
 int be_policy_destroy(be_policy* pol) {
   if (!pol) return BE_OK;
   const DeviceGuard dg(pol->cv.device);   // the caller's current device is restored on return
-  if (pol->img) (void)hipFree(pol->img);
-  if (pol->obs4) (void)hipFree(pol->obs4);
-  if (pol->zero4) (void)hipFree(pol->zero4);
-  delete pol;
+  policy_release(pol);
   return BE_OK;
 }
 
@@ -339,11 +327,10 @@ int be_policy_load(be_policy* pol, const float* fc1_w, const float* fc1_b, const
   be_ctx* ctx = pol->ctx;
   if (!fc1_w || !fc1_b || !act_w || !act_b || !val_w || !val_b)
     return be_ctx_fail(ctx, BE_E_INVALID, "be_policy_load: a weight pointer is NULL");
-  const DeviceGuard dg(pol->cv.device);   // the caller's current device is restored on return
-  POL_TRY(ctx, dg.err);
+  BE_ENTER_DEVICE(be_ctx_err(ctx), pol->cv.device);
   const PolPack a{fc1_w, fc1_b, act_w, act_b, val_w, val_b, pol->H, pol->F, pol->A};
   hipLaunchKernelGGL(policy_pack_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a, pol->img, pol->L);
-  POL_TRY(ctx, hipGetLastError());
+  if (int rc = be_launched(be_ctx_err(ctx))) return rc;
   // table pass: the dense forward of the 4 empty-window obs, into the image's table
   PParams p;
   memset(&p, 0, sizeof p);
@@ -351,7 +338,7 @@ int be_policy_load(be_policy* pol, const float* fc1_w, const float* fc1_b, const
   p.table_out = (float*)(pol->img + pol->L.table);
   p.n = 4; p.F = pol->F; p.A = pol->A; p.img_bytes = pol->L.total;
   hipLaunchKernelGGL(pol->k.fn, dim3(1), dim3(POL_THREADS), (size_t)pol->L.lds, (hipStream_t)stream, p);
-  POL_TRY(ctx, hipGetLastError());
+  if (int rc = be_launched(be_ctx_err(ctx))) return rc;
   pol->loaded = true;
   return BE_OK;
 }
@@ -363,8 +350,7 @@ int be_policy_act(be_policy* pol, const be_state* st, const uint8_t* obs, const 
   if (!pol->loaded) return be_ctx_fail(ctx, BE_E_INVALID, "be_policy_act before be_policy_load");
   if (!st || !st->episode || !st->ep_len || !obs || !out || !out->action)
     return be_ctx_fail(ctx, BE_E_INVALID, "be_policy_act needs state episode/ep_len, obs and out->action");
-  const DeviceGuard dg(pol->cv.device);   // the caller's current device is restored on return
-  POL_TRY(ctx, dg.err);
+  BE_ENTER_DEVICE(be_ctx_err(ctx), pol->cv.device);
   PParams p;
   memset(&p, 0, sizeof p);
   p.img = pol->img; p.obs = obs; p.episode = st->episode; p.ep_len = st->ep_len;
@@ -373,8 +359,7 @@ int be_policy_act(be_policy* pol, const be_state* st, const uint8_t* obs, const 
   p.gid0 = (int32_t)(uint32_t)pol->cv.env_offset; p.img_bytes = pol->L.total; p.dbg = pol->dbg;
   const dim3 grid((unsigned)((p.n + POL_ENVS - 1) / POL_ENVS));
   hipLaunchKernelGGL(pol->k.fn, grid, dim3(POL_THREADS), (size_t)pol->L.lds, (hipStream_t)stream, p);
-  POL_TRY(ctx, hipGetLastError());
-  return BE_OK;
+  return be_launched(be_ctx_err(ctx));
 }
 
 int be_policy_rollout(be_policy* pol, const be_state* st, const uint8_t* obs_in, uint8_t* obs_last, int32_t steps,
@@ -393,8 +378,7 @@ int be_policy_rollout(be_policy* pol, const be_state* st, const uint8_t* obs_in,
     return be_ctx_fail(ctx, BE_E_INVALID,
                        "be_policy_rollout needs 16-byte aligned obs buffers and num_envs * (4+W*W) % 16 == 0");
   if (steps == 0) return BE_OK;
-  const DeviceGuard dg(pol->cv.device);   // the caller's current device is restored on return
-  POL_TRY(ctx, dg.err);
+  BE_ENTER_DEVICE(be_ctx_err(ctx), pol->cv.device);
   const be_pol_rollout_args r{pol->img, pol->L.total, pol->k.HT, pol->k.KS, pol->k.NO, pol->A,
                               (unsigned long long)seed, obs_in, obs_last, steps, out, act};
   const int rc = be_internal_policy_rollout(ctx, st, &r, stream);
@@ -405,18 +389,13 @@ int be_policy_rollout(be_policy* pol, const be_state* st, const uint8_t* obs_in,
     const be_act_out ao{act->action + s * N, act->log_prob ? act->log_prob + s * N : nullptr,
                         act->value ? act->value + s * N : nullptr, nullptr};
     if (int e = be_policy_act(pol, st, o_in, &ao, seed, stream)) return e;
-    be_out o = *out;
-    o.obs = out->obs ? out->obs + s * N * F : obs_last;
-    o.reward = out->reward + s * N;
-    o.done = out->done + s * N;
-    if (o.truncated) o.truncated = out->truncated + s * N;
-    if (o.final_return) o.final_return = out->final_return + s * N;
-    if (o.final_len) o.final_len = out->final_len + s * N;
+    be_out o = behost::be_out_at(*out, s, N, F);
+    if (!o.obs) o.obs = obs_last;
     if (int e = be_step(ctx, st, ao.action, nullptr, nullptr, &o, stream)) return e;
   }
   if (out->obs && obs_last)
-    POL_TRY(ctx, hipMemcpyAsync(obs_last, out->obs + (steps - 1) * N * F, (size_t)(N * F), hipMemcpyDeviceToDevice,
-                                (hipStream_t)stream));
+    BE_HIP_TRY(be_ctx_err(ctx), hipMemcpyAsync(obs_last, out->obs + (steps - 1) * N * F, (size_t)(N * F),
+                                               hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return BE_OK;
 }
 

@@ -251,8 +251,12 @@ int be_load_state(be_ctx* ctx, const be_state* st, const void* blob, void* strea
  * way -- the pool changes timing only.  be_reset and be_load_state fill it after their own work,
  * and be_step queues a fill every `period` step launches (default 128; BALLENV_POOL_PERIOD, and
  * BALLENV_POOL=0 disables the pool, for A/B runs).  The pool serves one state: the one last
- * reset or loaded (or the first stepped); steps of any other state draw every reset inline, so
- * entries are only read and written by launches the caller already orders on one stream.
+ * reset, loaded or filled for (or the first stepped); steps of any other state draw every reset
+ * inline.  The library does not order the pool's launches itself: the caller must order, on one
+ * stream (or with events), every launch that uses a context's pool -- the owner's steps, resets,
+ * loads and fills, and across a change of owner the previous owner's launches before the new
+ * owner's reset / load / fill.  Two states of one context driven from unordered streams must not
+ * trade ownership (keep one owner, or disable the pool).
  * be_pool_fill: fill now (every env's stale entries) and make st the pool's state.
  * be_pool_invalidate: mark every entry unwritten (async on the stream): the inline path until the
  * next fill.  be_pool_set_period / be_pool_period: step launches per fill (0: only the explicit ones).
@@ -265,7 +269,7 @@ int64_t be_pool_bytes(const be_ctx* ctx);
 /* Test hook (synchronous; device-wide sync first): read (write = 0) or overwrite (write = 1) env's
  * entry in slot (0 / 1: the slot of episode x is x & 1).  words: TAG, AGENT, GOAL, ROWS0..2, then
  * the NS + ND obstacles' packed xy (6 + 13 + 5 words); f64: PREV, TOTAL.  ROWS0 bit 30 marks a
- * written entry, bit 31 a rejection-limit hit (layout: csrc/step_types.h, "the autoreset pool"). */
+ * written entry, bit 31 a rejection-limit hit (layout: csrc/pool_layout.h). */
 int be_pool_entry(be_ctx* ctx, int32_t env, int32_t slot, uint32_t* words, double* f64, int32_t write);
 
 /* ---- on-GPU select_action for batched rollouts (BASELINE config 5) ----
@@ -472,8 +476,10 @@ int be_board_status(be_board* b, int32_t* status_out, void* stream);
 /* The board's autoreset pool (as be_pool_* above): with Philox autoreset and one lane
  * per env, be_board_reset queues a fill of every env's next two episodes' resets and be_board_step
  * one every 128 steps (BALLENV_POOL_PERIOD), and the steps of the state last reset copy a current
- * entry where they would draw the reset inline -- the same bits either way.  BALLENV_POOL=0 at
- * create disables it.  Bytes held (0: no pool). */
+ * entry where they would draw the reset inline -- the same bits either way.  The same ordering
+ * contract holds: the caller orders every launch that uses a board's pool on one stream, a change
+ * of owner (be_board_reset of another state) included.  BALLENV_POOL=0 at create disables it.
+ * Bytes held (0: no pool). */
 int64_t be_board_pool_bytes(const be_board* b);
 
 #ifdef __cplusplus
