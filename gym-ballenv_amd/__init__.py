@@ -28,7 +28,8 @@ def __getattr__(name):
     if name in ("Policy", "HipPolicy", "torch_select_action"):
         from . import policy
         return getattr(policy, name)
-    if name in ("Rollout", "a2c_losses", "a2c_update", "a2c_targets", "A2CTargets", "A2CGrad"):
+    if name in ("Rollout", "a2c_losses", "a2c_update", "a2c_targets", "A2CTargets", "A2CGrad", "HipAdam",
+                "A2CTrainer"):
         from . import rollout
         return getattr(rollout, name)
     if name == "BatchedBoard":
@@ -43,4 +44,4 @@ def __getattr__(name):
 __all__ = ["EnvConfig", "MOVE_LIST", "step_bytes", "survey_step_bytes", "Box", "Discrete", "BallEnvError", "BatchedBallEnv",
            "BallEnv", "make", "TimeLimit", "shard", "gather_stats", "combine_stats", "Policy", "HipPolicy",
            "torch_select_action", "Rollout", "a2c_losses", "a2c_update", "a2c_targets", "A2CTargets",
-           "A2CGrad", "BatchedBoard"]
+           "A2CGrad", "HipAdam", "A2CTrainer", "BatchedBoard"]

@@ -31,7 +31,7 @@ EXPORTS = ("be_abi_version", "be_config_default", "be_config_check", "be_step_by
            "be_board_config_default", "be_board_create", "be_board_destroy", "be_board_last_error",
            "be_board_reset", "be_board_step", "be_board_rollout", "be_board_observe", "be_board_status",
            "be_board_pool_bytes")
-# be_a2c_targets, be_a2c_grad and be_a2c_grad_workspace_bytes are declared and exported too; the
+# be_a2c_targets, be_a2c_grad, be_a2c_grad_workspace_bytes and be_a2c_adam are declared and exported too; the
 # loader below checks them by name like the rest (sig)
 BOARD_MAX_STATIC, BOARD_MAX_ACTIONS, BOARD_FEATURES = 32, 16, 20
 
@@ -86,6 +86,11 @@ class BeA2CGrads(C.Structure):
     _fields_ = [("fc1_weight", C.c_void_p), ("fc1_bias", C.c_void_p), ("action_head_weight", C.c_void_p),
                 ("action_head_bias", C.c_void_p), ("value_head_weight", C.c_void_p), ("value_head_bias", C.c_void_p),
                 ("losses", C.c_void_p)]
+
+
+class BeA2CTensors(C.Structure):
+    _fields_ = [("fc1_weight", C.c_void_p), ("fc1_bias", C.c_void_p), ("action_head_weight", C.c_void_p),
+                ("action_head_bias", C.c_void_p), ("value_head_weight", C.c_void_p), ("value_head_bias", C.c_void_p)]
 
 
 class BeBoardConfig(C.Structure):
@@ -167,6 +172,8 @@ def lib() -> C.CDLL:
         "be_a2c_targets": (C.c_int, [vp, vp, vp, vp, vp, i32, C.c_double, C.c_double, P(BeA2COut), vp]),
         "be_a2c_grad_workspace_bytes": (i64, [vp, i32, i32]),
         "be_a2c_grad": (C.c_int, [vp, vp, vp, vp, vp, i64, P(BeA2CWeights), vp, i64, P(BeA2CGrads), vp]),
+        "be_a2c_adam": (C.c_int, [vp, P(BeA2CTensors), P(BeA2CTensors), P(BeA2CTensors), P(BeA2CTensors), vp,
+                                  C.c_double, C.c_double, C.c_double, vp, vp, i32, vp]),
         "be_board_config_default": (C.c_int, [P(BeBoardConfig), i32, i32]),
         "be_board_create": (C.c_int, [P(BeBoardConfig), i32, P(vp)]),
         "be_board_destroy": (C.c_int, [vp]),
@@ -183,7 +190,7 @@ def lib() -> C.CDLL:
     diag = bool(os.environ.get("BALLENV_LIB"))
     for name, (res, args) in sig.items():
         fn = getattr(L, name, None)
-        if fn is None and diag and (name.startswith("be_pool_") or name == "be_board_pool_bytes"):
+        if fn is None and diag and (name.startswith("be_pool_") or name in ("be_board_pool_bytes", "be_a2c_adam")):
             continue
         if fn is None:
             raise BallEnvError(f"{LIB_PATH} does not export {name}: rebuild it")

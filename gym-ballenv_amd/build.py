@@ -19,6 +19,8 @@ object) and linked into one shared library:
   csrc/a2c_grad.hip A2C losses and Policy gradients of recorded rows (f32 MFMAs; no VGPR_MFMA:
                     its accumulators live for the whole kernel, and with them in VGPRs the W = 10
                     instance measured 14 % slower, W = 5 the same: profiles/a2c_grad_ab.json)
+  csrc/a2c_adam.hip the Adam step on the six Policy tensors and the re-pack of the policy image (f64
+                    operations with -ffp-contract=off, as every unit: the pinned arithmetic has no FMA)
 """
 from __future__ import annotations
 
@@ -44,7 +46,7 @@ VGPR_MFMA = ["-mllvm", "-amdgpu-mfma-vgpr-form"]
 # prologue); the compiler keeps an s_load entry for firmware without the preload.
 KARG_PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
 UNITS = {"ballenv.hip": [*VGPR_MFMA, *KARG_PRELOAD], "abi.hip": [], "policy.hip": ["-fno-slp-vectorize", *VGPR_MFMA],
-         "features.hip": [], "board.hip": [], "a2c.hip": [], "a2c_grad.hip": []}
+         "features.hip": [], "board.hip": [], "a2c.hip": [], "a2c_grad.hip": [], "a2c_adam.hip": []}
 HEADERS = [HDR, *(os.path.join(CSRC, h) for h in ("philox.h", "internal.h", "host_logic.h", "pool_layout.h", "policy_core.h", "diag.h",
                                               "step_types.h"))]
 

@@ -89,6 +89,21 @@ inline int be_ctx_fail(be_ctx* ctx, int code, const char* msg) { return be_fail(
 // an entry point's ctx and be_state pointer checks ("ctx is NULL" first; BE_OK or a be_ctx_fail code)
 __attribute__((visibility("hidden"))) int be_ctx_check_state(be_ctx* ctx, const be_state* st);
 
+// What another unit may know of a be_policy (policy.hip): its packed image on the device and the
+// shape it was created for (pol_layout(HT, KS, NO) in policy_core.h is the image's layout).
+struct be_policy_view {
+  be_ctx* ctx;
+  uint8_t* img;
+  int32_t HT, KS, NO;          // the layout pick_policy chose
+  int32_t H, F, A;             // hidden, 4 + W*W, num_actions
+  int32_t device;
+};
+__attribute__((visibility("hidden"))) be_policy_view be_policy_get(const be_policy* pol);
+// The table pass behind a rewritten image (be_policy_load, be_a2c_adam): the dense forward of the four
+// empty-window observations into the image's table, on `stream`; marks the policy loaded.  The
+// caller has entered the policy's device.  BE_OK or an error code recorded in the ctx.
+__attribute__((visibility("hidden"))) int be_internal_policy_table(be_policy* pol, void* stream);
+
 // fused config-5 rollout (be_policy_rollout -> rollout_kernel with the policy in the loop)
 struct be_pol_rollout_args {
   const uint8_t* img;          // packed Policy(W) image (device)

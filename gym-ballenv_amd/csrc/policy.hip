@@ -63,41 +63,25 @@ __global__ void policy_pack_kernel(PolPack a, uint8_t* img, PolLayout L) {
   const int m = threadIdx.x;
   if (m >= L.HT * 16) return;
   int32_t* bias = (int32_t*)(img + L.bias);
-  float* head = (float*)(img + L.head);
   float* hb = (float*)(img + L.hbias);
   const bool real = m < a.H;
   float mx = 0.f;
-  if (real) {
+  if (real)
     for (int k = 0; k < a.F; ++k) mx = fmaxf(mx, fabsf(a.w1[(int64_t)m * a.F + k]));
-    mx = fmaxf(mx, fabsf(a.b1[m]) * (1.0f / 64.0f));
-  }
-  const double s = mx > 0.f ? (double)(float)((double)mx / 8323072.0) : 1.0;   // 127 * 2^16
-  bias[m] = real ? (int32_t)llrint((double)a.b1[m] / s) : 0;
-  const int ht = m >> 4, row = m & 15;
+  const double s = pol_row_step(mx, real ? a.b1[m] : 0.f);
+  bias[m] = real ? pol_quant_bias(a.b1[m], s) : 0;
   for (int k = 0; k < L.KS * 64; ++k) {
-    long long q = 0;
-    if (real && k < a.F) {
-      q = llrint((double)a.w1[(int64_t)m * a.F + k] / s);
-      q = q > 8323072 ? 8323072 : (q < -8323072 ? -8323072 : q);
-    }
-    const int d0 = (int)(((q + 128) & 255) - 128);
-    const long long q1 = (q - d0) >> 8;
-    const int d1 = (int)(((q1 + 128) & 255) - 128);
-    const int d2 = (int)((q1 - d1) >> 8);
-    const int ks = k >> 6, g = (k >> 4) & 3, j = k & 15, lane = row + 16 * g;
-    const int dig[3] = {d2, d1, d0};
-    for (int d = 0; d < 3; ++d)
-      img[L.frag + ((((ht * 3 + d) * L.KS + ks) * 64 + lane) * 16 + j)] = (uint8_t)(int8_t)dig[d];
+    const bool live = real && k < a.F;
+    pol_store_digits(img, L, m, k, live, live ? a.w1[(int64_t)m * a.F + k] : 0.f, s);
   }
   // head weights, scaled by s_k: output o < A -> action_head[o], o == NO-1 -> value_head, else 0
-  const int g = (m >> 2) & 3, r = m & 3;
   for (int o = 0; o < L.NO; ++o) {
     double w = 0.0;
     if (real) {
       if (o < a.A) w = a.wa[(int64_t)o * a.H + m];
       else if (o == L.NO - 1) w = a.wv[m];
     }
-    head[((ht * 4 + g) * L.NO + o) * 4 + r] = (float)(w * s);
+    pol_store_head(img, L, m, o, w, s);
   }
   if (m < L.NO) hb[m] = m < a.A ? a.ba[m] : (m == L.NO - 1 ? a.bv[0] : -INFINITY);
 }
@@ -331,7 +315,18 @@ int be_policy_load(be_policy* pol, const float* fc1_w, const float* fc1_b, const
   const PolPack a{fc1_w, fc1_b, act_w, act_b, val_w, val_b, pol->H, pol->F, pol->A};
   hipLaunchKernelGGL(policy_pack_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a, pol->img, pol->L);
   if (int rc = be_launched(be_ctx_err(ctx))) return rc;
-  // table pass: the dense forward of the 4 empty-window obs, into the image's table
+  return be_internal_policy_table(pol, stream);
+}
+
+}  // extern "C"
+
+be_policy_view be_policy_get(const be_policy* pol) {
+  return {pol->ctx, pol->img, pol->k.HT, pol->k.KS, pol->k.NO, pol->H, pol->F, pol->A, pol->cv.device};
+}
+
+// table pass: the dense forward of the 4 empty-window obs, into the image's table
+int be_internal_policy_table(be_policy* pol, void* stream) {
+  be_ctx* ctx = pol->ctx;
   PParams p;
   memset(&p, 0, sizeof p);
   p.img = pol->img; p.obs = pol->obs4; p.episode = pol->zero4; p.ep_len = (const int32_t*)pol->zero4;
@@ -342,6 +337,8 @@ int be_policy_load(be_policy* pol, const float* fc1_w, const float* fc1_b, const
   pol->loaded = true;
   return BE_OK;
 }
+
+extern "C" {
 
 int be_policy_act(be_policy* pol, const be_state* st, const uint8_t* obs, const be_act_out* out, uint64_t seed,
                   void* stream) {

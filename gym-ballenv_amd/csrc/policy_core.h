@@ -41,6 +41,38 @@ __host__ __device__ constexpr PolLayout pol_layout(int HT, int KS, int NO) {
   return L;
 }
 
+// One fc1 row's fixed-point form (the notes at the top of policy.hip), shared by be_policy_load's pack
+// kernel (policy.hip) and the Adam step's re-pack (a2c_adam.hip): the same operations in the same
+// order, so the same bytes.
+// The row's step s_k from mx = max|W1[k, :]| (0 for a padded row) and its bias.
+__device__ __forceinline__ double pol_row_step(float mx, float b1) {
+  mx = fmaxf(mx, fabsf(b1) * (1.0f / 64.0f));
+  return mx > 0.f ? (double)(float)((double)mx / 8323072.0) : 1.0;   // 127 * 2^16
+}
+__device__ __forceinline__ int32_t pol_quant_bias(float b1, double s) { return (int32_t)llrint((double)b1 / s); }
+// Element (m, k) of the padded fc1 matrix into the fragment image: q = rint(w / s) (0 where !live: a
+// padded row or column), as three signed int8 digits, high plane first.
+__device__ __forceinline__ void pol_store_digits(uint8_t* img, const PolLayout& L, int m, int k, bool live, float w,
+                                                 double s) {
+  long long q = 0;
+  if (live) {
+    q = llrint((double)w / s);
+    q = q > 8323072 ? 8323072 : (q < -8323072 ? -8323072 : q);
+  }
+  const int d0 = (int)(((q + 128) & 255) - 128);
+  const long long q1 = (q - d0) >> 8;
+  const int d1 = (int)(((q1 + 128) & 255) - 128);
+  const int d2 = (int)((q1 - d1) >> 8);
+  const int ht = m >> 4, row = m & 15, ks = k >> 6, g = (k >> 4) & 3, j = k & 15, lane = row + 16 * g;
+  const int dig[3] = {d2, d1, d0};
+  for (int d = 0; d < 3; ++d)
+    img[L.frag + ((((ht * 3 + d) * L.KS + ks) * 64 + lane) * 16 + j)] = (uint8_t)(int8_t)dig[d];
+}
+// Output o of hidden unit m in the head image: (W_o,m * s_m) in f32 (w = 0 for a pad output or row).
+__device__ __forceinline__ void pol_store_head(uint8_t* img, const PolLayout& L, int m, int o, double w, double s) {
+  const int ht = m >> 4, g = (m >> 2) & 3, r = m & 3;
+  ((float*)(img + L.head))[((ht * 4 + g) * L.NO + o) * 4 + r] = (float)(w * s);
+}
 
 // Sum over the 4 lane groups (lanes l, l^16, l^32, l^48) of four values at once: lane group
 // (row) r gets the full sum of value r, added as ((g0 + g1) + (g2 + g3)) -- two permlane16

@@ -29,6 +29,9 @@ return normalisation, policy + value losses) over all envs at once, so a
 training loop is rollout (HIP) -> update (torch autograd) -> re-pack (HIP).
 ``A2CGrad`` (``a2c_update(grads="hip")``) is the losses and ``loss.backward()``
 of that update in one HIP entry (``be_a2c_grad``), straight from the u8 record.
+``HipAdam`` is ``optimizer.step()`` and the re-pack in one HIP entry (``be_a2c_adam``), and
+``A2CTrainer`` the loop rollout -> targets -> gradients -> Adam -> re-packed policy with no host
+round trip between two rollouts, its update half replayed as one HIP graph.
 """
 from __future__ import annotations
 
@@ -174,6 +177,147 @@ class A2CGrad:
         return pl, vl, int(n)
 
 
+def _beta_powers(t: int, betas):
+    """(beta1^t, beta2^t) as be_a2c_adam's state holds them after t steps: the running f64 products,
+    one multiply per step (``beta ** t`` differs in the last bits)."""
+    p1 = p2 = 1.0
+    for _ in range(int(t)):
+        p1 *= float(betas[0])
+        p2 *= float(betas[1])
+    return p1, p2
+
+
+class HipAdam:
+    """``be_a2c_adam`` bound to one ``HipPolicy`` and its ``Policy`` module: ``torch.optim.Adam``
+    (weight_decay=0, amsgrad=False, maximize=False) on the six parameters in place *and* the re-pack of
+    the new weights into ``hip_policy``, in one asynchronous entry (include/ballenv.h pins the
+    arithmetic; reproducible bit for bit).  After ``step()`` ``policy.state_dict()`` is current and
+    the policy kernels run the new weights: no ``HipPolicy.load`` is needed.
+
+    Owns the moments (``exp_avg`` / ``exp_avg_sq``, keyed like ``policy.state_dict()``), the device
+    ``state`` [t, beta1^t, beta2^t, lr] and, with ``log_rows`` > 0, a (log_rows, 3) f64 ``loss_log``
+    ring: the step that starts at count t copies the ``losses`` it is given into row t % log_rows.
+    Nothing is allocated per call and nothing synchronises, so a step can be graph-captured; the
+    learning rate lives on the device, so a captured step follows ``opt.lr = ...``."""
+
+    def __init__(self, hip_policy: HipPolicy, policy: Policy, lr: float = 1e-3, betas=(0.9, 0.999),
+                 eps: float = 1e-8, log_rows: int = 0):
+        self.hp, self.policy = hip_policy, policy
+        self.env = env = hip_policy.env
+        self._lib = _abi.lib()
+        dev = env.device
+        H, A, F = hip_policy.hidden, hip_policy.num_actions, env.obs_dim
+        self._shapes = dict(zip(_PARAMS, ((H, F), (H,), (A, H), (A,), (1, H), (1,))))
+        self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
+        if not (0.0 <= self.betas[0] < 1.0 and 0.0 <= self.betas[1] < 1.0) or self.eps < 0.0 or lr < 0.0:
+            raise ValueError("HipAdam needs betas in [0, 1), eps >= 0 and lr >= 0")
+        self._params()                      # ValueError for a module this HipPolicy was not made for
+        self.exp_avg = {k: torch.zeros(s, dtype=torch.float32, device=dev) for k, s in self._shapes.items()}
+        self.exp_avg_sq = {k: torch.zeros(s, dtype=torch.float32, device=dev) for k, s in self._shapes.items()}
+        self._lr = float(lr)
+        self.state = torch.tensor([0.0, 1.0, 1.0, self._lr], dtype=torch.float64, device=dev)
+        self.loss_log = torch.zeros(int(log_rows), 3, dtype=torch.float64, device=dev) if log_rows > 0 else None
+        self._m = _abi.BeA2CTensors(*(self.exp_avg[k].data_ptr() for k in _PARAMS))
+        self._v = _abi.BeA2CTensors(*(self.exp_avg_sq[k].data_ptr() for k in _PARAMS))
+        self._keep = None
+
+    def _check(self, what: str, k: str, x) -> torch.Tensor:
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or not x.is_contiguous() or \
+                x.device != self.env.device or tuple(x.shape) != self._shapes[k]:
+            raise ValueError(f"{what} {k} must be a contiguous f32 tensor of shape {self._shapes[k]} on the "
+                             "HipPolicy's device")
+        return x
+
+    def _params(self):
+        ps = dict(self.policy.named_parameters())
+        if set(ps) != set(_PARAMS):
+            raise ValueError("HipAdam needs a Policy module (fc1, action_head, value_head)")
+        return [self._check("policy parameter", k, ps[k].detach()) for k in _PARAMS]
+
+    def step(self, grads=None, losses: Optional[torch.Tensor] = None) -> None:
+        """One Adam step and the re-pack, asynchronous on the caller's current stream.
+        grads: ``A2CGrad.grads`` (a dict keyed like ``policy.state_dict()``), default: the parameters'
+        ``.grad``.  losses: the 3 f64 of ``A2CGrad`` on the device, logged if there is a ``loss_log``."""
+        ws = self._params()
+        if grads is None:
+            ps = dict(self.policy.named_parameters())
+            if any(ps[k].grad is None for k in _PARAMS):
+                raise ValueError("HipAdam.step() without grads= needs every parameter's .grad")
+            gs = [self._check("gradient of", k, ps[k].grad) for k in _PARAMS]
+        else:
+            gs = [self._check("gradient of", k, grads[k]) for k in _PARAMS]
+        lp = gp = None
+        if losses is not None and self.loss_log is not None:
+            if losses.dtype != torch.float64 or losses.numel() != 3 or not losses.is_contiguous() or \
+                    losses.device != self.env.device:
+                raise ValueError("losses must be 3 contiguous f64 on the HipPolicy's device")
+            lp, gp = losses.data_ptr(), self.loss_log.data_ptr()
+        w = _abi.BeA2CTensors(*(x.data_ptr() for x in ws))
+        g = _abi.BeA2CTensors(*(x.data_ptr() for x in gs))
+        rc = self._lib.be_a2c_adam(self.hp._h, C.byref(w), C.byref(g), C.byref(self._m), C.byref(self._v),
+                                   self.state.data_ptr(), self.betas[0], self.betas[1], self.eps, lp, gp,
+                                   0 if gp is None else self.loss_log.shape[0], self.env._stream())
+        if rc:
+            _abi.check(rc, self.env._ctx)
+        self._keep = (ws, gs, losses)       # alive until the kernels have run
+
+    def zero_grad(self, set_to_none: bool = True) -> None:
+        self.policy.zero_grad(set_to_none=set_to_none)
+
+    @property
+    def lr(self) -> float:
+        return self._lr
+
+    @lr.setter
+    def lr(self, value: float) -> None:
+        self._lr = float(value)
+        self.state[3:].fill_(self._lr)      # stream-ordered: steps enqueued earlier keep the old rate
+
+    def step_count(self) -> int:
+        """Steps taken so far (synchronises)."""
+        return int(self.state[0].item())
+
+    def state_dict(self) -> dict:
+        """``torch.optim.Adam.state_dict()``'s format, parameters in ``policy.parameters()`` order, so
+        ``torch.optim.Adam(policy.parameters()).load_state_dict(...)`` continues this run (synchronises)."""
+        t = self.step_count()
+        groups = torch.optim.Adam(self.policy.parameters(), lr=self._lr, betas=self.betas,
+                                  eps=self.eps).state_dict()["param_groups"]
+        state = {}
+        if t > 0:
+            state = {i: {"step": torch.tensor(float(t)), "exp_avg": self.exp_avg[k].clone(),
+                         "exp_avg_sq": self.exp_avg_sq[k].clone()} for i, k in enumerate(_PARAMS)}
+        return {"state": state, "param_groups": groups}
+
+    def load_state_dict(self, sd: dict) -> None:
+        """From ``state_dict()`` of a HipAdam or of a ``torch.optim.Adam`` over ``policy.parameters()``.
+        beta^t is rebuilt by the repeated f64 product the device runs, so a HipAdam round trip
+        continues bit for bit."""
+        if len(sd["param_groups"]) != 1 or len(sd["param_groups"][0]["params"]) != len(_PARAMS):
+            raise ValueError("HipAdam needs one parameter group over the six Policy parameters")
+        grp = sd["param_groups"][0]
+        if grp.get("weight_decay", 0) != 0 or grp.get("amsgrad", False) or grp.get("maximize", False):
+            raise ValueError("HipAdam has no weight_decay, amsgrad or maximize")
+        st = sd["state"]
+        steps = {int(float(st[i]["step"])) for i in st}
+        if st and (len(st) != len(_PARAMS) or len(steps) != 1):
+            raise ValueError("HipAdam needs the state of all six parameters at one common step")
+        t = steps.pop() if st else 0
+        for k in _PARAMS:
+            i = grp["params"][_PARAMS.index(k)]
+            for mine, key in ((self.exp_avg, "exp_avg"), (self.exp_avg_sq, "exp_avg_sq")):
+                if st:
+                    if tuple(st[i][key].shape) != self._shapes[k]:
+                        raise ValueError(f"{key} of {k} has the wrong shape")
+                    mine[k].copy_(st[i][key])
+                else:
+                    mine[k].zero_()
+        self.betas, self.eps, self._lr = (float(grp["betas"][0]), float(grp["betas"][1])), float(grp["eps"]), \
+            float(grp["lr"])
+        p1, p2 = _beta_powers(t, self.betas)
+        self.state.copy_(torch.tensor([float(t), p1, p2, self._lr], dtype=torch.float64))
+
+
 class Rollout:
     def __init__(self, env, policy: Policy, horizon: int, backend: str = "hip", record_obs: bool = False,
                  seed: int = 0x5E1EC7, chunk: int = 100):
@@ -266,8 +410,9 @@ class Rollout:
             self.step(t)
         self.end()
 
-    def capture(self, chunk: int = 250) -> None:
-        """Record the T steps into HIP graphs of ``chunk`` steps each."""
+    def capture(self, chunk: int = 250, stream: Optional[torch.cuda.Stream] = None) -> None:
+        """Record the T steps into HIP graphs of ``chunk`` steps each (stream: the stream to capture
+        on; default a new one from torch's pool)."""
         dev = self.env.device
         if self.backend == "fused":     # a few launches per horizon: nothing to capture
             self._graphs = []
@@ -277,7 +422,7 @@ class Rollout:
             with torch.no_grad():
                 self.policy(self.env.obs[:64].float())
             torch.cuda.synchronize(dev)
-        cap = torch.cuda.Stream(dev)
+        cap = torch.cuda.Stream(dev) if stream is None else stream
         self._graphs = []
         for c0 in range(0, self.T, chunk):
             g = torch.cuda.CUDAGraph()
@@ -397,6 +542,10 @@ def _a2c_update_hip_grads(rollout: "Rollout", optimizer, gamma: float, targets: 
     if ag is None or ag.policy is not rollout.policy:
         ag = rollout._a2c_grad = A2CGrad(rollout.env, rollout.policy)
     grads = ag(rollout.obs[:-1], rollout.actions, Rn, valid)
+    if isinstance(optimizer, HipAdam):      # straight from A2CGrad's tensors: no .grad copies, no second load
+        optimizer.step(grads, ag._losses)
+        pl, vl, _ = ag.losses()
+        return pl + vl
     for k, prm in rollout.policy.named_parameters():
         if prm.grad is None:
             prm.grad = grads[k].clone()
@@ -421,6 +570,9 @@ def a2c_update(rollout: "Rollout", optimizer, gamma: float = 0.99, targets: str 
         raise ValueError("targets must be 'torch' or 'hip'")
     if grads not in ("torch", "hip"):
         raise ValueError("grads must be 'torch' or 'hip'")
+    hip_adam = isinstance(optimizer, HipAdam)
+    if hip_adam and (optimizer.hp is not rollout.hp or optimizer.policy is not rollout.policy):
+        raise ValueError("the HipAdam must be bound to rollout.hp and rollout.policy")
     if grads == "hip":
         return _a2c_update_hip_grads(rollout, optimizer, gamma, targets)
     tg = None
@@ -433,6 +585,82 @@ def a2c_update(rollout: "Rollout", optimizer, gamma: float = 0.99, targets: str 
     optimizer.zero_grad()
     loss.backward()
     optimizer.step()
-    if rollout.hp is not None:
+    if rollout.hp is not None and not hip_adam:      # a HipAdam step has re-packed rollout.hp
         rollout.hp.load(rollout.policy)
     return float(loss.detach())
+
+
+class A2CTrainer:
+    """The A2C training loop with no host round trip between two rollouts: per iteration
+    rollout -> ``a2c_targets_into`` -> ``A2CGrad`` -> ``HipAdam.step`` (which re-packs the policy), all
+    enqueued on the caller's current stream with nothing allocated and no synchronise.
+
+    Owns a ``Rollout(record_obs=True)`` (``backend="fused"``: ``be_policy_rollout`` launches;
+    ``"hip"``: the policy and step kernels, graph-replayed after ``capture()``), preallocated
+    ``A2CTargets``, an ``A2CGrad`` and a ``HipAdam`` (``.opt``; ``log_rows`` sizes its loss log).
+    ``capture()`` records the update half (targets, gradients, Adam + re-pack, loss log) into one HIP
+    graph, a linear chain on one stream, which ``train()`` then replays after each rollout."""
+
+    def __init__(self, env, policy: Policy, horizon: int, gamma: float = 0.99, backend: str = "fused",
+                 lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, seed: int = 0x5E1EC7, log_rows: int = 0,
+                 chunk: int = 100):
+        import numpy as np
+        if backend not in ("fused", "hip"):
+            raise ValueError("backend must be 'fused' or 'hip'")
+        self.env, self.policy, self.gamma = env, policy, float(gamma)
+        self.rollout = Rollout(env, policy, horizon, backend=backend, record_obs=True, seed=seed, chunk=chunk)
+        T, N, dev = self.rollout.T, env.num_envs, env.device
+        self.targets = A2CTargets(torch.zeros(T, N, dtype=torch.float32, device=dev), None,
+                                  torch.zeros(T, N, dtype=torch.uint8, device=dev), None)
+        self.grad = A2CGrad(env, policy)
+        self.opt = HipAdam(self.rollout.hp, policy, lr=lr, betas=betas, eps=eps, log_rows=log_rows)
+        self._eps = float(np.finfo(np.float32).eps)
+        self._graph = None
+
+    def update(self) -> None:
+        """The update half on the recorded rollout: targets, gradients, Adam step + re-pack."""
+        ro = self.rollout
+        a2c_targets_into(self.env, ro.rewards, ro.dones, None, self.gamma, self._eps, None, self.targets)
+        g = self.grad(ro.obs[:-1], ro.actions, self.targets.returns_norm, self.targets.valid)
+        self.opt.step(g, self.grad._losses)
+
+    def capture(self, stream: Optional[torch.cuda.Stream] = None) -> None:
+        """Record ``update()`` into one HIP graph (and, for backend="hip", the rollout into its own:
+        ``Rollout.capture``).  stream: the stream to capture on; default a new one from torch's pool."""
+        dev = self.env.device
+        cap = torch.cuda.Stream(dev) if stream is None else stream
+        if self.rollout.backend == "hip":
+            self.rollout.capture(stream=cap)
+        torch.cuda.synchronize(dev)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=cap):
+            self.update()
+        torch.cuda.synchronize(dev)
+        self._graph = g
+
+    def train(self, iterations: int) -> None:
+        """``iterations`` times rollout + update, enqueued without a synchronise."""
+        ro = self.rollout
+        for _ in range(int(iterations)):
+            if ro.backend == "hip" and not ro._graphs:
+                ro.run_eager()
+            else:
+                ro.run()
+            if self._graph is not None:
+                self._graph.replay()
+            else:
+                self.update()
+
+    def losses(self) -> torch.Tensor:
+        """The loss log as (iterations, 3) f64 on the host -- policy loss, value loss, active rows of
+        each iteration, the last ``log_rows`` of them once the ring has wrapped (synchronises)."""
+        log = self.opt.loss_log
+        if log is None:
+            raise ValueError("A2CTrainer(log_rows=...) keeps the loss log")
+        t, rows = self.opt.step_count(), log.shape[0]
+        out = log[:t] if t <= rows else torch.roll(log, -(t % rows), 0)
+        return out.cpu()
+
+    def close(self) -> None:
+        self._graph = None
+        self.rollout.close()

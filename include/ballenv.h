@@ -401,6 +401,43 @@ int be_a2c_grad(be_ctx* ctx, const uint8_t* obs, const uint8_t* actions, const f
                 const uint8_t* valid, int64_t rows, const be_a2c_weights* weights, void* workspace,
                 int64_t workspace_bytes, const be_a2c_grads* grads, void* stream);
 
+/* ---- the Adam step and the policy re-pack: optimizer.step() (examples/ball_cnn_ac3.py:244, :505) ----
+ * One Adam step (torch.optim.Adam with weight_decay = 0, amsgrad = False, maximize = False) on the
+ * six Policy tensors in place, and `pol`'s packed image rebuilt from the new weights: afterwards
+ * the image holds the bytes be_policy_load would build from them, so be_policy_act / be_policy_rollout
+ * run the updated policy.  pol's ctx, F = 4 + W*W, hidden and num_actions define every shape; a
+ * policy that was never loaded is accepted (the step defines the whole image).
+ * All tensors are contiguous f32 device arrays in state_dict layout: params (updated), grads (read:
+ * what be_a2c_grad writes), exp_avg and exp_avg_sq (updated; zeros for a fresh optimizer).
+ * state: 4 f64 on the device, [t, beta1^t, beta2^t, lr]; a fresh optimizer holds [0, 1, 1, lr].
+ * The learning rate lives on the device so that a captured graph follows a change of it.
+ * The arithmetic is pinned; every operation is one f64 operation, no FMA:
+ *   t' = t + 1;  p1' = p1 * beta1;  p2' = p2 * beta2         (state after the call: [t', p1', p2', lr])
+ *   bc1 = 1 - p1';  bc2s = sqrt(1 - p2');  ss = lr / bc1
+ *   per element:  g = (double)grad
+ *     m' = (float)(beta1 * (double)m + (1 - beta1) * g)
+ *     v' = (float)(beta2 * (double)v + ((1 - beta2) * g) * g)
+ *     w' = (float)((double)w - ss * ((double)m' / (sqrt((double)v') / bc2s + eps)))
+ * Every element is computed from the state as it was before the call; the state advances exactly
+ * once per call, after all of them (a one-thread kernel behind the update kernel on `stream`).
+ * losses / loss_log: both NULL, or losses = the 3 f64 of be_a2c_grads.losses and loss_log a
+ * (log_rows, 3) f64 device array, log_rows >= 1: row (t mod log_rows) receives a copy of losses, t
+ * being the state's step count before the call -- a replayed graph logs every iteration's losses.
+ * Asynchronous on `stream`, no allocation and no synchronisation (graph-capturable); three
+ * launches: the update + pack kernel, the state kernel, the empty-window table pass.        */
+typedef struct be_a2c_tensors {           /* six f32 device arrays, state_dict layout             */
+  float* fc1_weight;                /* (hidden, F)                                             */
+  float* fc1_bias;                  /* (hidden)                                                */
+  float* action_head_weight;        /* (num_actions, hidden)                                   */
+  float* action_head_bias;          /* (num_actions)                                           */
+  float* value_head_weight;         /* (1, hidden)                                             */
+  float* value_head_bias;           /* (1)                                                     */
+} be_a2c_tensors;
+
+int be_a2c_adam(be_policy* pol, const be_a2c_tensors* params, const be_a2c_tensors* grads,
+                const be_a2c_tensors* exp_avg, const be_a2c_tensors* exp_avg_sq, double* state, double beta1,
+                double beta2, double eps, const double* losses, double* loss_log, int32_t log_rows, void* stream);
+
 /* ---- the createBoard physics profile ----
  * N independent ballenv_pygame.createBoard worlds (reset :460-513, step :650-675,
  * calc_reward :680-706) with the 20 featureExtractor features (featureExtractor.py:247-265)
