@@ -7,6 +7,45 @@ import torch
 PARAMS = ("fc1.weight", "fc1.bias", "action_head.weight", "action_head.bias", "value_head.weight", "value_head.bias")
 
 
+HIDDEN = {10: 208, 5: 128, 7: 72, 11: 256}      # the hidden size of a case that names none
+
+# Cases (W, hidden, num_actions, rows) of tests/test_gpu_a2c_grad.py that the host test checks too
+# (tests/test_a2c_grad_host.py::test_new_cases_kink_share).
+# Shapes: A and hidden off the multiples the kernel pads to, each W, both sides of the instance
+# bounds (hidden 128 / 129 at W = 5, 208 / 209 at W = 10), hidden tiles 14 .. 16.
+SHAPE_CASES = [(5, 1, 1, 130), (7, 17, 15, 200), (10, 100, 5, 333), (5, 129, 9, 300), (5, 127, 9, 301),
+               (5, 256, 4, 300), (1, 16, 3, 200), (2, 33, 2, 129), (3, 16, 1, 70), (4, 64, 9, 192),
+               (6, 65, 7, 260), (8, 240, 9, 321), (9, 200, 14, 500), (10, 256, 9, 257), (10, 209, 9, 257)]
+TILE_EDGE_CASES = [(10, 208, 9, 64), (10, 208, 9, 65), (5, 128, 9, 128)]
+
+
+def multi_tile_cases(slots):
+    """{name: (W, hidden, num_actions, rows, fixture)} with more than one 64-row tile per workgroup of
+    a persistent grid of `slots` workgroups (workgroup b takes the tiles b, b + slots, ...)."""
+    return {"w10": (10, 208, 9, 64 * (2 * slots + 5) + 37, False),      # 3 tiles or 2; the partial tile in round 3
+            "w10-fixture": (10, 208, 9, 64 * (2 * slots + 5) + 37, True),
+            "w5": (5, 128, 9, 64 * 3 * slots, False),                   # exactly 3 rounds
+            "w11": (11, 256, 15, 64 * (slots + 3) + 1, False),          # 3 second tiles, the last of one row
+            "w7": (7, 72, 9, 64 * (2 * slots + 1), False)}
+
+
+def case_policy(W, hidden=None, num_actions=9, fixture=False):
+    """The Policy of a case: the committed fixture, or torch.manual_seed(0)'s initialisation."""
+    from gym_ballenv_amd.policy import Policy, reference_weights
+    if fixture:
+        pol = Policy.from_npz(reference_weights(W), W)
+        assert (pol.hidden_layer, pol.action_head.out_features) == (hidden or HIDDEN[W], num_actions)
+        return pol
+    torch.manual_seed(0)
+    return Policy(W, hidden=hidden or HIDDEN[W], num_actions=num_actions)
+
+
+def case_inputs(pol, W, rows, num_actions=9):
+    """make_inputs with seed 1000 + rows, and the relu-kink rows of `pol` among them."""
+    obs, actions, rn, valid = make_inputs(np.random.default_rng(1000 + rows), rows, W, num_actions)
+    return obs, actions, rn, valid, kink_rows(weights64(pol), obs)
+
+
 def weights64(policy):
     """The six arrays of a Policy as numpy f64, keyed like state_dict()."""
     return {k: v.detach().cpu().double().numpy() for k, v in policy.state_dict().items()}

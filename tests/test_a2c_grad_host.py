@@ -9,7 +9,8 @@ import subprocess
 import numpy as np
 import torch
 
-from a2c_grad_ref import PARAMS, a2c_grad_ref, kink_rows, make_inputs, torch_reference, weights64
+from a2c_grad_ref import (PARAMS, SHAPE_CASES, TILE_EDGE_CASES, a2c_grad_ref, case_inputs, case_policy, kink_rows,
+                          make_inputs, multi_tile_cases, torch_reference, weights64)
 from gym_ballenv_amd import _abi
 from gym_ballenv_amd.policy import Policy
 
@@ -67,6 +68,21 @@ def test_fixture_weights_kink_share():
     share = kink_rows(weights64(pol), obs).mean()
     print(f"kink share, fixture weights: {share:.4%}")
     assert share <= 0.01
+
+
+def test_new_cases_kink_share():
+    """Every multi-tile (at 256 workgroups: an MI355X), shape and tile-edge case of the GPU test: at
+    most 1 % of its rows lie on a relu kink (the GPU test clears their valid under the same cap) and
+    at least half of the rows stay valid."""
+    cases = [c + (False,) for c in SHAPE_CASES + TILE_EDGE_CASES] + list(multi_tile_cases(256).values())
+    assert len(cases) == 23 and all(rows > 64 * 256 for _, _, _, rows, _ in multi_tile_cases(256).values())
+    for W, hidden, A, rows, fixture in cases:
+        pol = case_policy(W, hidden, A, fixture)
+        obs, actions, rn, valid, kink = case_inputs(pol, W, rows, A)
+        left = int((np.where(kink, 0, valid) != 0).sum())
+        print(f"W={W} hidden={hidden} A={A} rows={rows} fixture={fixture}: {kink.sum()} kink rows, {left} valid")
+        assert kink.sum() <= 0.01 * rows, (W, hidden, A, rows, fixture, int(kink.sum()))
+        assert left >= 0.5 * rows and (actions < A).all(), (W, hidden, A, rows, fixture, left)
 
 
 def test_library_declares_and_exports_be_a2c_grad():

@@ -1,6 +1,11 @@
 """be_a2c_grad on the GPU: against torch f64 autograd under the project's error rule
 (tests/test_gpu_policy.py), exact zeros when nothing is active, inactive rows, bit-reproducible,
-graph-capturable, the A2CGrad wrapper, a2c_update(grads="hip") and the argument checks."""
+graph-capturable, the A2CGrad wrapper, a2c_update(grads="hip") and the argument checks.
+
+The kernel's grid is persistent (one workgroup per CU, each looping over 64-row tiles), so the
+multi-tile tests size their rows from the device's CU count and assert rows > 64 CUs: against f64,
+a later round alone against a stand-alone call byte for byte, and observations off the 4-byte grid
+(fetch_tile's byte path) against the aligned call byte for byte."""
 import copy
 import ctypes as C
 import functools
@@ -9,12 +14,12 @@ import numpy as np
 import pytest
 import torch
 
-from a2c_grad_ref import PARAMS, a2c_grad_ref, kink_rows, make_inputs, torch_reference, weights64
+from a2c_grad_ref import (PARAMS, SHAPE_CASES, TILE_EDGE_CASES, a2c_grad_ref, case_inputs, case_policy, kink_rows,
+                          make_inputs, multi_tile_cases, torch_reference, weights64)
 
 pytestmark = pytest.mark.gpu
 
 SENTINEL = 12345.0
-HIDDEN = {10: 208, 5: 128, 7: 72, 11: 256}
 
 
 def _env(gpu, W, N=64, seed=3):
@@ -22,23 +27,26 @@ def _env(gpu, W, N=64, seed=3):
     return gb.BatchedBallEnv(N, W, gb.EnvConfig(), device=gpu, seed=seed)
 
 
-def _policy(W, fixture=False):
-    from gym_ballenv_amd.policy import Policy, reference_weights
-    if fixture:
-        return Policy.from_npz(reference_weights(W), W)
-    torch.manual_seed(0)
-    return Policy(W, hidden=HIDDEN[W])
+def _slots(gpu):
+    """Workgroups of be_a2c_grad's persistent grid on this device: what grad_slots() queries."""
+    return min(torch.cuda.get_device_properties(gpu).multi_processor_count, 1024)
+
+
+def _policy(W, fixture=False, hidden=None, num_actions=9):
+    return case_policy(W, hidden, num_actions, fixture)
 
 
 @functools.lru_cache(maxsize=None)
-def _case(W, rows, fixture=False):
+def _case(W, rows, fixture=False, hidden=None, num_actions=9, force_valid=False):
     """Policy, inputs with the relu-kink rows' valid cleared (at most 1 % of the rows), the f64
-    reference (torch f64 autograd on the CPU) and the restatement's loss scales.  Computed once."""
-    pol = _policy(W, fixture)
+    reference (torch f64 autograd on the CPU) and the restatement's loss scales.  Computed once.
+    hidden=None: HIDDEN[W].  force_valid: every row's valid is 1 before the kink rows are cleared."""
+    pol = _policy(W, fixture, hidden, num_actions)
     # seed 1000 + rows: with seed `rows` one of the 63 rows of the (10, 63) case lies on a kink (> 1 %)
-    obs, actions, rn, valid = make_inputs(np.random.default_rng(1000 + rows), rows, W)
-    kink = kink_rows(weights64(pol), obs)
+    obs, actions, rn, valid, kink = case_inputs(pol, W, rows, num_actions)
     assert kink.sum() <= 0.01 * rows, f"{kink.sum()} of {rows} rows on a relu kink"
+    if force_valid:
+        valid = np.ones_like(valid)
     valid = np.where(kink, 0, valid).astype(np.uint8)
     g64, l64 = torch_reference(pol, obs, actions, rn, valid, torch.float64)
     ref = a2c_grad_ref(weights64(pol), obs, actions, rn, valid)
@@ -49,18 +57,45 @@ def _case(W, rows, fixture=False):
 def _run(gpu, ag, obs, actions, rn, valid):
     """One A2CGrad call on sentinel-filled outputs: ({name: f32 numpy}, losses f64 numpy)."""
     t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(gpu)
+    return _run_t(gpu, ag, t(obs), t(actions), t(rn), t(valid))
+
+
+def _run_t(gpu, ag, obs, actions, rn, valid):
+    """_run on device tensors, passed to A2CGrad as they are."""
     for g in ag.grads.values():
         g.fill_(SENTINEL)
     ag._losses.fill_(SENTINEL)
-    ag(t(obs), t(actions), t(rn), t(valid))
+    ag(obs, actions, rn, valid)
     torch.cuda.synchronize(gpu)
     return {k: v.cpu().numpy().copy() for k, v in ag.grads.items()}, ag._losses.cpu().numpy().copy()
 
 
-def _assert_rule(got, losses, g64, l64, g32, l32, abs_terms, tag):
-    """err_hip <= 4 * err_torch32 + 1e-6 per gradient tensor (max-abs error against f64 over the f64
-    tensor's max-abs) and per loss (over the f64 sum of the absolute terms)."""
+def _same_bytes(a, b, tag):
+    (ga, la), (gb, lb) = a, b
+    assert la.tobytes() == lb.tobytes(), (tag, la, lb)
     for k in PARAMS:
+        assert ga[k].tobytes() == gb[k].tobytes(), (tag, k, float(np.abs(ga[k] - gb[k]).max()))
+
+
+# With one action log pi = 0 whatever the weights: the f64 action-head gradients and the policy loss
+# are identically zero, and the kernel's must be too (its expf(z - lse) - 1 is exact there).
+ZERO_AT_A1 = ("action_head.weight", "action_head.bias", "policy_loss")
+
+
+def _assert_rule(got, losses, g64, l64, g32, l32, abs_terms, tag, zero=()):
+    """err_hip <= 4 * err_torch32 + 1e-6 per gradient tensor (max-abs error against f64 over the f64
+    tensor's max-abs) and per loss (over the f64 sum of the absolute terms).  The tensors and losses
+    named in `zero` have an all-zero f64 reference instead, and the kernel's are all zero."""
+    for k in zero:
+        if k in PARAMS:
+            assert (g64[k] == 0).all() and (got[k] == 0).all(), (tag, k)
+        else:
+            i = ("policy_loss", "value_loss").index(k)
+            assert abs_terms[i] == 0 and l64[i] == 0 and losses[i] == 0, (tag, k, losses[i])
+        print(f"{tag} {k}: exact zero")
+    for k in PARAMS:
+        if k in zero:
+            continue
         scale = np.abs(g64[k]).max()
         assert scale > 0, (tag, k)
         e_hip = np.abs(got[k].astype(np.float64) - g64[k]).max() / scale
@@ -68,6 +103,8 @@ def _assert_rule(got, losses, g64, l64, g32, l32, abs_terms, tag):
         print(f"{tag} {k}: err_hip {e_hip:.3g} err_torch32 {e_t32:.3g}")
         assert np.isfinite(got[k]).all() and e_hip <= 4 * e_t32 + 1e-6, (tag, k, e_hip, e_t32)
     for i, name in enumerate(("policy_loss", "value_loss")):
+        if name in zero:
+            continue
         e_hip = abs(losses[i] - l64[i]) / abs_terms[i]
         e_t32 = abs(l32[i] - l64[i]) / abs_terms[i]
         print(f"{tag} {name}: err_hip {e_hip:.3g} err_torch32 {e_t32:.3g}")
@@ -79,10 +116,8 @@ CASES = [(10, 1, False), (10, 63, False), (10, 257, False), (10, 11951, False), 
          (11, 321, False)]       # the bounds (F = 125, hidden 256): the kernel instance for any shape
 
 
-@pytest.mark.parametrize("W,rows,fixture", CASES)
-def test_against_f64(gpu, W, rows, fixture):
+def _check_against_f64(gpu, c, W, tag, zero=()):
     from gym_ballenv_amd import A2CGrad
-    c = _case(W, rows, fixture)
     env = _env(gpu, W)
     pol = copy.deepcopy(c["pol"]).to(gpu)
     ag = A2CGrad(env, pol)
@@ -92,8 +127,122 @@ def test_against_f64(gpu, W, rows, fixture):
     if c["count"] == 0:             # a single row that drew valid = 0: exact zeros
         assert all((g == 0).all() for g in got.values()) and (losses == 0).all()
     else:
-        _assert_rule(got, losses, c["g64"], c["l64"], g32, l32, c["abs_terms"], f"W={W} rows={rows}")
+        _assert_rule(got, losses, c["g64"], c["l64"], g32, l32, c["abs_terms"], tag, zero)
     env.close()
+
+
+@pytest.mark.parametrize("W,rows,fixture", CASES)
+def test_against_f64(gpu, W, rows, fixture):
+    _check_against_f64(gpu, _case(W, rows, fixture), W, f"W={W} rows={rows}")
+
+
+@pytest.mark.parametrize("name", list(multi_tile_cases(1)))
+def test_against_f64_multi_tile(gpu, name):
+    """More than one tile per workgroup, sized from this device's CU count: the prefetch of the next
+    tile, its store after step 5, the fetch past the end, the per-row inputs of a later tile and the
+    accumulators that live across tiles, under test_against_f64's rule."""
+    slots = _slots(gpu)
+    W, hidden, A, rows, fixture = multi_tile_cases(slots)[name]
+    assert rows > 64 * slots, (rows, slots)
+    c = _case(W, rows, fixture, hidden, A)
+    assert c["count"] > 0.5 * rows
+    _check_against_f64(gpu, c, W, f"multi-tile {name} W={W} hidden={hidden} A={A} rows={rows} slots={slots}")
+
+
+@pytest.mark.parametrize("W,hidden,A,rows", SHAPE_CASES + TILE_EDGE_CASES)
+def test_against_f64_shapes(gpu, W, hidden, A, rows):
+    """The padding guards (h < H, j < A, j == A, bz) off the multiples of 8 / 16, every W, both sides
+    of each kernel instance's bounds, and rows at a tile's edge."""
+    c = _case(W, rows, False, hidden, A)
+    assert c["count"] > 0
+    _check_against_f64(gpu, c, W, f"W={W} hidden={hidden} A={A} rows={rows}", ZERO_AT_A1 if A == 1 else ())
+
+
+def test_single_active_row_w5(gpu):
+    """(5, 1) of test_against_f64 drew valid = 0; here the row is valid and its action in range."""
+    c = _case(5, 1, force_valid=True)
+    assert c["count"] == 1 and c["valid"][0] == 1 and c["actions"][0] < 9
+    _check_against_f64(gpu, c, 5, "W=5 one active row")
+
+
+def _rounds(gpu, W, rows, first_tile, slots):
+    """make_inputs' rows with valid cleared before tile `first_tile` and from tile first_tile + slots on:
+    the whole run against a stand-alone call on the tiles that stay active, byte for byte."""
+    from gym_ballenv_amd import A2CGrad
+    pol = _policy(W)
+    obs, actions, rn, valid = make_inputs(np.random.default_rng(1000 + rows), rows, W)
+    lo, hi = 64 * first_tile, min(64 * (first_tile + slots), rows)
+    valid = valid.copy()
+    valid[:lo] = 0
+    valid[hi:] = 0
+    n = int(valid.sum())
+    assert n > 0.5 * (hi - lo) and (actions < 9).all()
+    env = _env(gpu, W)
+    ag = A2CGrad(env, copy.deepcopy(pol).to(gpu))
+    whole = _run(gpu, ag, obs, actions, rn, valid)
+    s = slice(lo, hi)
+    alone = _run(gpu, ag, obs[s], actions[s], rn[s], valid[s])
+    assert whole[1][2] == n and alone[1][2] == n
+    assert all(np.abs(g).max() > 0 for g in alone[0].values())
+    _same_bytes(whole, alone, (W, rows, first_tile))
+    env.close()
+
+
+@pytest.mark.parametrize("k", [1, 2])
+def test_later_round_alone_is_bit_identical(gpu, k):
+    """Only round k's tiles are active (workgroup b's tile b + k slots): inactive rows, with their
+    random observations and actions, add exact +0, so the result is the stand-alone call's."""
+    slots = _slots(gpu)
+    rows = 64 * 3 * slots
+    assert rows > 64 * slots
+    _rounds(gpu, 10, rows, k * slots, slots)
+
+
+def test_partial_last_round_alone_is_bit_identical(gpu):
+    """Active only in round 3's five whole tiles and its 37-row tile; the stand-alone call launches six
+    workgroups, and the slots it lacks would have added +0 in the reduction."""
+    slots = _slots(gpu)
+    rows = 64 * (2 * slots + 5) + 37
+    assert rows > 64 * slots
+    _rounds(gpu, 10, rows, 2 * slots, slots)
+
+
+def _unaligned(gpu, W, rows):
+    """obs at byte offset o F of an aligned buffer (fetch_tile's byte path) against the aligned call."""
+    from gym_ballenv_amd import A2CGrad
+    F = 4 + W * W
+    pol = _policy(W)
+    obs, actions, rn, valid = make_inputs(np.random.default_rng(1000 + rows), rows, W)
+    t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(gpu)
+    obs_t, rest = t(obs), (t(actions), t(rn), t(valid))
+    assert obs_t.data_ptr() % 4 == 0
+    env = _env(gpu, W)
+    ag = A2CGrad(env, copy.deepcopy(pol).to(gpu))
+    aligned = _run_t(gpu, ag, obs_t, *rest)
+    assert aligned[1][2] == int(valid.sum()) and all(np.abs(g).max() > 0 for g in aligned[0].values())
+    for o in (1, 2, 3):
+        buf = torch.full((rows + o, F), 255, dtype=torch.uint8, device=gpu)
+        assert buf.data_ptr() % 4 == 0
+        shifted = buf[o:]
+        shifted.copy_(obs_t)
+        assert shifted.is_contiguous() and shifted.data_ptr() == buf.data_ptr() + o * F
+        if (F * o) % 4:
+            assert shifted.data_ptr() % 4 != 0
+        _same_bytes(_run_t(gpu, ag, shifted, *rest), aligned, (W, rows, o))
+    env.close()
+
+
+@pytest.mark.parametrize("W", [5, 7, 11])
+def test_unaligned_obs_is_bit_identical(gpu, W):
+    assert (4 + W * W) % 2 == 1          # odd F: every offset o F, o = 1 .. 3, is off the 4-byte grid
+    _unaligned(gpu, W, 300)
+
+
+def test_unaligned_obs_multi_tile(gpu):
+    slots = _slots(gpu)
+    rows = multi_tile_cases(slots)["w5"][3]
+    assert rows > 64 * slots
+    _unaligned(gpu, 5, rows)
 
 
 def test_nothing_active(gpu):
