@@ -1739,10 +1739,14 @@ struct Step2Lds {
   static constexpr int bytes = SLOTS * S2_CT * 4 + (S2_CT / 2) * Geo<WT>::F;
 };
 static_assert(S2_CT != 256 || Step2Lds<10, 13, 5>::bytes == 24576, "the default shape's LDS");
-template <int WT, int NSC, int NDC, bool POOL = false>
+// where step2_kernel's KParams argument lies in its kernarg segment: six pointers and two ints, KHot
+// on the next 64-byte line, then the KParams (KFn2, step_types.h)
+constexpr int S2_KPARAMS_AT = (6 * 8 + 2 * 4 + 63) / 64 * 64 + (int)sizeof(KHot);
+static_assert(S2_KPARAMS_AT == 128 && alignof(KParams) <= 64, "step2_kernel's kernarg layout");
+template <int WT, int NSC, int NDC, bool POOL = false, bool PREVR = true>
 __global__ __launch_bounds__(S2_CT, 2) void step2_kernel(const Tables* a_tables, uint32_t* a_episode, int32_t* a_ep_len,
                                                          int32_t* a_dyn_obs, uint8_t* a_dyn_goal, int32_t* a_static_obs,
-                                                         int32_t a_n, int32_t a_gid0, KHot hot_in, KParams p) {
+                                                         int32_t a_n, int32_t a_gid0, KHot hot_in, KParams p_arg) {
   const KHot hot = {hot_in.agent, hot_in.goal, hot_in.prev_dist, hot_in.total_dist, hot_in.ep_return,
                     hot_in.actions, hot_in.stats, hot_in.prev_read, hot_in.goal_change};
   __builtin_amdgcn_sched_barrier(0);   // KHot's scalar load stays in front of everything below
@@ -1760,7 +1764,10 @@ __global__ __launch_bounds__(S2_CT, 2) void step2_kernel(const Tables* a_tables,
   constexpr int TW = (int)(sizeof(TablesX) / 16);   // 16-byte table words
 
   DIAG(0);
-  if (DBG(DBG_EXIT_ENTRY)) return;
+  {
+    [[maybe_unused]] const KParams& p = p_arg;   // (diagnostics builds: KParams::dbg)
+    if (DBG(DBG_EXIT_ENTRY)) return;
+  }
   const int N = a_n, tid = (int)threadIdx.x, w = tid >> 6, lane = tid & 63, h = lane & 1;
   DIAG_SARG(0, N);
   const int blk0 = (int)blockIdx.x * EPB, i = blk0 + (tid >> 1), e0 = blk0 + w * EPW;
@@ -1795,33 +1802,48 @@ __global__ __launch_bounds__(S2_CT, 2) void step2_kernel(const Tables* a_tables,
 #pragma unroll
   for (int j = 0; j < SS; ++j) so[j] = ld_s(a_static_obs, (uint32_t)min(L * j + h, NSC - 1) * (uint32_t)N + ic);
   // (every load above goes through a preloaded argument; the ones below through KHot, the one
-  // scalar load that the prologue waits for)
+  // scalar load that the prologue waits for.  With no branch left in the prologue it is one
+  // scheduling region: the two barriers keep the loads above in front of the wait for KHot -- the
+  // scheduler had moved five static-obstacle loads behind the action -- and KParams' scalar loads
+  // below behind the action, out of that wait)
+  __builtin_amdgcn_sched_barrier(0);
   const int32_t agent0 = ld_s(hot.agent, ic), goal0 = ld_s(hot.goal, ic);
-  // state[2] of the last step (prev_read = 0: recomputed, it is calc_dist(goal, agent) -- see KParams).
-  // (Read unconditionally with the select after a scheduling barrier, so that the action is issued
-  // with the other loads instead of after the goal load lands: 5.26-5.27 against 5.22-5.24 us at
-  // 32 768 envs, the same within noise at 65 536 -- profiles/r05_prologue_ab.txt, not kept here; it
-  // is kept in the one-lane kernel, 8.05 against 8.13-8.15 us at 131 072)
+  // state[2] of the last step (prev_read = 0, the PREVR = false instances: recomputed, it is
+  // calc_dist(goal, agent) -- see KParams).  Read unconditionally, also where the recompute then
+  // replaces it: vmcnt retires in order, and with a vector load inside a branch the waitcnt pass
+  // cannot tell whether it was issued, so every later wait counts only the loads that certainly
+  // were -- with this load behind `if (hot.prev_read)` the wait in front of ep_len's first use (the
+  // Philox block) also covered agent, goal, prev_dist and total_dist, the loads through KHot
+  // (profiles/r09_step2_exact_waits_isa.txt).  No load from here to the action's first
+  // use sits in a branch or under an exec mask, and with prev_read a template parameter no branch
+  // at all stands between the first load and the split on `done`.
   DIAG_SARG(1, hot.prev_read);
-  // (prev_read = 0 recomputes after the barrier: here the goal load would have to land before the
-  // loads below issue, which costs 0.2 us -- profiles/r08_kernarg_preload_ab.txt)
-  double old_dist = 0.0;
-  if (hot.prev_read) old_dist = ld_s(hot.prev_dist, ic);
+  const double old_read = ld_s(hot.prev_dist, ic);
   const double total = ld_s(hot.total_dist, ic);
   double ret = ld_s(hot.ep_return, ic);
   // the action last: the obstacle draws and moves below need no action, so a row that misses the
   // caches (a pre-sampled action tape) delays only the work that needs it (6.46 -> 6.37 us with
-  // cache-resident rows, 6.92 -> 6.79 us with rows from HBM)
+  // cache-resident rows, 6.92 -> 6.79 us with rows from HBM).  It is the prologue's last vector
+  // load, so the wait in front of the agent move is for the action alone.
   const int a = ld_s(hot.actions, ic);
-  // the wave's stats slot (one per 32 envs), read now: a wave with a finished env updates it at the
-  // end of its finishing path, and a dependent load there would lengthen exactly the waves that reset
+  __builtin_amdgcn_sched_barrier(0);
+  // KParams, read from here on.  A by-value struct argument is copied at function entry, so its
+  // scalar loads sit at the top of the entry block: while a branch followed the loads above, the
+  // compiler sank them into the block behind it; with the prologue straight-line they would stay on
+  // top, in front of the wait for KHot: 5.41-5.46 against the parent's 5.27-5.33 us per launch,
+  // profiles/r09_step2_exact_waits_ab.txt (and in the `false` instance one of them then reused an SGPR
+  // of KHot's, which put that wait in front of every vector load).  So the copy is taken here, from
+  // the argument's place in the kernarg segment, through a pointer the compiler cannot see through.
+  typedef const KParams __attribute__((address_space(4)))* KArgs;
+  uint64_t kargs = (uint64_t)__builtin_amdgcn_kernarg_segment_ptr() + S2_KPARAMS_AT;
+  asm volatile("" : "+s"(kargs));
+  KParams p = *(const KParams*)(KArgs)kargs;
+  // (what the Philox block needs right behind the barrier comes with KHot's load, at entry)
+  p.inv_g1 = p_arg.inv_g1;
+  p.seed = p_arg.seed;
+  // the wave's stats slot (one per 32 envs): read at the head of the finishing path, by the waves
+  // that fold into it (the tail below)
   double* const slot = hot.stats ? hot.stats + (size_t)(e0 / 32) * 8 : nullptr;
-  double2 sp0 = make_double2(0.0, 0.0), sp1 = sp0, sp2 = sp0;
-  if (slot && lane == 0 && e0 < N) {
-    sp0 = reinterpret_cast<const double2*>(slot)[0];
-    sp1 = reinterpret_cast<const double2*>(slot)[1];
-    sp2 = reinterpret_cast<const double2*>(slot)[2];
-  }
   // the output / state pointers that both paths after the split store through, read here, ahead
   // of the split: read where they are used, each path began with its own chain of scalar loads
   // (one round trip after another in front of the physics stores).  KParams is first read here,
@@ -1884,9 +1906,14 @@ __global__ __launch_bounds__(S2_CT, 2) void step2_kernel(const Tables* a_tables,
   const v2u boxw = {(unsigned short)nb0.bw, (unsigned short)nb0.bh};
   const v2s agv = __builtin_bit_cast(v2s, pk(ax, ay));
   const double dist = calc_dist(gx, gy, ax, ay);
-  if (!hot.prev_read) {
-    // (on copies the compiler cannot see through: sharing the unpacking with the move above, it
-    // put the wait for the goal load in front of this branch, ahead of the Philox block)
+  double old_dist = old_read;
+  if constexpr (!PREVR) {
+    // (A/B only, an instance of its own: as a run-time branch on hot.prev_read it cut the physics in
+    // two scheduling regions, with the Philox block behind the branch and the tables' LDS reads in
+    // front of it, and their wait -- which also covers KParams' scalar loads -- in the Philox block:
+    // 5.21-5.28 us per launch with the branch, 5.14-5.17 without, profiles/r09_step2_exact_waits_ab.txt.
+    // On copies the compiler cannot see through: sharing the unpacking with the move above, it
+    // put the wait for the goal load ahead of the Philox block)
     int32_t g0 = goal0, a0 = agent0;
     asm("" : "+v"(g0), "+v"(a0));
     old_dist = calc_dist(px(g0), py(g0), px(a0), py(a0));
@@ -1991,6 +2018,20 @@ __global__ __launch_bounds__(S2_CT, 2) void step2_kernel(const Tables* a_tables,
     // vmcnt down to them at their first use, after the stores and the raster below.  Only
     // the ~15 waves of a launch with a finished env read these ~4 KB.  (POOL instances are launched
     // only with KParams::pool set: be_step picks them by it.)
+    // (FIN) the wave's stats slot, 48 bytes, ahead of the entries and not waited for until fold(),
+    // which runs after the copy-out: the whole finishing path covers the round trip.  Every lane
+    // loads the same address (no exec mask; a finishing wave has e0 < N), behind one uniform branch
+    // on the slot being there; older than the entry loads, it changes none of their counted waits.
+    // The lean path never reads the slot: in the prologue these three loads were the last ones
+    // issued, and the wait for the action covered them in every wave.
+    double2 sp0 = make_double2(0.0, 0.0), sp1 = sp0, sp2 = sp0;
+    if constexpr (FIN) {
+      if (slot) {
+        sp0 = reinterpret_cast<const double2*>(slot)[0];
+        sp1 = reinterpret_cast<const double2*>(slot)[1];
+        sp2 = reinterpret_cast<const double2*>(slot)[2];
+      }
+    }
     uint2 q_tv = make_uint2(0u, 0u);
     uint4 qb[7];
     if constexpr (FIN && POOL) {
@@ -3415,6 +3456,7 @@ Launch pick_kernel(const be_config& c, int mode, bool fixed_ok, int lanes10, int
     // two lanes per env: 32 envs per wave, 128 per block
     L.kind = KIND_STEP2; L.consumes_pool = true;
     L.fn2 = pool ? step2_kernel<10, FIX_NS, FIX_ND, true> : step2_kernel<10, FIX_NS, FIX_ND, false>;
+    L.fn2_recompute = pool ? step2_kernel<10, FIX_NS, FIX_ND, true, false> : step2_kernel<10, FIX_NS, FIX_ND, false, false>;
     L.epb = S2_CT / 2; L.threads = S2_CT; L.lds = Step2Lds<10, FIX_NS, FIX_ND>::bytes;
     snprintf(L.name, sizeof L.name, "step2_kernel<10, %d, %d, %s>", FIX_NS, FIX_ND, pv);
     return L;
@@ -3501,7 +3543,7 @@ Launch pick_pool_fill(int window) {
 void launch_kernel(const Launch& L, const KParams& a, hipStream_t stream) {
   const dim3 grid((unsigned)((a.n + L.epb - 1) / L.epb)), block((unsigned)L.threads);
   if (L.fn2)
-    hipLaunchKernelGGL(L.fn2, grid, block, (size_t)L.lds, stream, a.tables, a.episode, a.ep_len, a.dyn_obs, a.dyn_goal,
+    hipLaunchKernelGGL(a.prev_read ? L.fn2 : L.fn2_recompute, grid, block, (size_t)L.lds, stream, a.tables, a.episode, a.ep_len, a.dyn_obs, a.dyn_goal,
                        a.static_obs, a.n, a.gid0,
                        KHot{a.agent, a.goal, a.prev_dist, a.total_dist, a.ep_return, a.actions, a.stats, a.prev_read,
                             a.goal_change},

@@ -131,6 +131,7 @@ enum Kind {
 struct Launch {
   KFn fn = nullptr;
   KFn2 fn2 = nullptr;            // step2_kernel (fn is nullptr then)
+  KFn2 fn2_recompute = nullptr;  // its KParams::prev_read = 0 instance (A/B only; launch_kernel picks by the flag)
   int kind = KIND_NONE;
   int epb = BLOCK_THREADS;       // envs per block
   int threads = BLOCK_THREADS;
