@@ -32,6 +32,10 @@ def __getattr__(name):
                 "A2CTrainer"):
         from . import rollout
         return getattr(rollout, name)
+    if name in ("BlockPolicy", "HipBlockPolicy", "BlockRollout", "torch_block_select_action", "reinforce_losses",
+                "reinforce_update", "reference_block_weights"):
+        from . import block_policy
+        return getattr(block_policy, name)
     if name == "BatchedBoard":
         from .board import BatchedBoard
         return BatchedBoard
@@ -44,4 +48,5 @@ def __getattr__(name):
 __all__ = ["EnvConfig", "MOVE_LIST", "step_bytes", "survey_step_bytes", "Box", "Discrete", "BallEnvError", "BatchedBallEnv",
            "BallEnv", "make", "TimeLimit", "shard", "gather_stats", "combine_stats", "Policy", "HipPolicy",
            "torch_select_action", "Rollout", "a2c_losses", "a2c_update", "a2c_targets", "A2CTargets",
-           "A2CGrad", "HipAdam", "A2CTrainer", "BatchedBoard"]
+           "A2CGrad", "HipAdam", "A2CTrainer", "BatchedBoard", "BlockPolicy", "HipBlockPolicy", "BlockRollout",
+           "torch_block_select_action", "reinforce_losses", "reinforce_update", "reference_block_weights"]

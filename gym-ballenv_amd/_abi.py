@@ -28,6 +28,7 @@ EXPORTS = ("be_abi_version", "be_config_default", "be_config_check", "be_step_by
            "be_status", "be_state_blob_bytes", "be_save_state", "be_load_state",
            "be_pool_fill", "be_pool_invalidate", "be_pool_set_period", "be_pool_period", "be_pool_bytes", "be_pool_entry", "be_policy_create", "be_policy_destroy", "be_policy_load", "be_policy_act",
            "be_policy_rollout", "be_policy_bytes", "be_observe_blocks",
+           "be_mlp_create", "be_mlp_destroy", "be_mlp_load", "be_mlp_act", "be_mlp_bytes",
            "be_board_config_default", "be_board_create", "be_board_destroy", "be_board_last_error",
            "be_board_reset", "be_board_step", "be_board_rollout", "be_board_observe", "be_board_status",
            "be_board_pool_bytes")
@@ -169,6 +170,11 @@ def lib() -> C.CDLL:
         "be_policy_rollout": (C.c_int, [vp, P(BeState), vp, vp, i32, P(BeOut), P(BeActOut), u64, vp]),
         "be_policy_bytes": (i64, [vp]),
         "be_observe_blocks": (C.c_int, [vp, P(BeState), vp, vp, vp]),
+        "be_mlp_create": (C.c_int, [vp, i32, i32, i32, i32, i32, P(vp)]),
+        "be_mlp_destroy": (C.c_int, [vp]),
+        "be_mlp_load": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp]),
+        "be_mlp_act": (C.c_int, [vp, P(BeState), vp, vp, P(BeActOut), u64, vp]),
+        "be_mlp_bytes": (i64, [vp]),
         "be_a2c_targets": (C.c_int, [vp, vp, vp, vp, vp, i32, C.c_double, C.c_double, P(BeA2COut), vp]),
         "be_a2c_grad_workspace_bytes": (i64, [vp, i32, i32]),
         "be_a2c_grad": (C.c_int, [vp, vp, vp, vp, vp, i64, P(BeA2CWeights), vp, i64, P(BeA2CGrads), vp]),
@@ -190,7 +196,8 @@ def lib() -> C.CDLL:
     diag = bool(os.environ.get("BALLENV_LIB"))
     for name, (res, args) in sig.items():
         fn = getattr(L, name, None)
-        if fn is None and diag and (name.startswith("be_pool_") or name in ("be_board_pool_bytes", "be_a2c_adam")):
+        if fn is None and diag and (name.startswith("be_pool_") or name.startswith("be_mlp_") or
+                                     name in ("be_board_pool_bytes", "be_a2c_adam")):
             continue
         if fn is None:
             raise BallEnvError(f"{LIB_PATH} does not export {name}: rebuild it")

@@ -1,0 +1,330 @@
+"""The reference's REINFORCE / supervised block-count policy and its batched, on-GPU select_action.
+
+Reference:
+* ``Policy``          examples/ball_env_reinforce.py:57-73 (and examples/test_model.py:57-85)
+                      affine1 (29 -> 128) -> relu -> affine2 (128 -> 128) -> relu -> affine3 (-> 9)
+                      -> relu -> softmax, on the ``prep_state2`` block counts (:130-172)
+* ``Model``           examples/train_supervise.py:11-28: the same layers, no relu on the last
+* ``select_action``   ball_env_reinforce.py:76-85   a ~ Categorical(probs); saved log_prob(a)
+* ``finish_episode``  ball_env_reinforce.py:88-108  R^ = (R - mean) / (std + eps); loss = sum -log_prob * R^
+* the stored weights  2 layers (affine2 is 9 x 128): ``with obs``, ``without obs_1``, ``without_obs_rand``;
+                      3 layers: ``supervised``
+
+``HipBlockPolicy`` runs that select_action for every env of a ``BatchedBallEnv`` in one launch of the
+kernel in csrc/mlp_policy.hip (``be_mlp_act``), which computes ``prep_state2`` of each env's state
+itself: the 29-byte row makes no round trip.  ``BlockRollout`` is the T-step loop of
+``be_mlp_act`` + ``be_step`` writing straight into (T, N) buffers, capturable into HIP graphs;
+``reinforce_losses`` / ``reinforce_update`` are the batched ``finish_episode`` over such a record
+(targets from ``be_a2c_targets``, gradients from torch autograd over the recorded rows).
+``torch_block_select_action`` is the same computation in plain PyTorch fp32 -- the numerics
+reference of the tests.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+from typing import Optional
+
+import numpy as np
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import _abi
+
+BLOCKS = 29                      # prep_state2's row: 4 quadrant + 5 x 5 blocks
+# be_mlp_act's work split (csrc/mlp_policy.hip): a persistent grid of one workgroup per compute unit,
+# WAVES waves each, a wave taking TILE envs per round (tile t of G workgroups: workgroup t % G, wave t // G % WAVES)
+TILE, WAVES = 16, 8
+_KINDS = ("supervised3", "reinforce2")
+
+
+class BlockPolicy(nn.Module):
+    """ball_env_reinforce.py:57-73 (the same parameter names, so the reference's state_dicts load).
+    layers=2: affine1 -> relu -> affine2 (-> actions); hidden: an int, or (hidden1, hidden2)."""
+
+    def __init__(self, layers: int = 3, hidden=128, num_actions: int = 9, final_relu: bool = True):
+        super().__init__()
+        if layers not in (2, 3):
+            raise ValueError("layers must be 2 or 3")
+        h1, h2 = (hidden, hidden) if isinstance(hidden, int) else (int(hidden[0]), int(hidden[1]))
+        self.layers, self.final_relu, self.num_actions = int(layers), bool(final_relu), int(num_actions)
+        self.hidden1, self.hidden2 = int(h1), int(h2) if layers == 3 else 0
+        self.affine1 = nn.Linear(BLOCKS, self.hidden1)
+        if layers == 3:
+            self.affine2 = nn.Linear(self.hidden1, self.hidden2)
+            self.affine3 = nn.Linear(self.hidden2, self.num_actions)
+        else:
+            self.affine2 = nn.Linear(self.hidden1, self.num_actions)
+
+    def logits(self, x):
+        x = F.relu(self.affine1(x))
+        if self.layers == 3:
+            x = self.affine3(F.relu(self.affine2(x)))
+        else:
+            x = self.affine2(x)
+        return F.relu(x) if self.final_relu else x
+
+    def forward(self, x):
+        return F.softmax(self.logits(x), dim=-1)
+
+    def linears(self):
+        return [self.affine1, self.affine2] + ([self.affine3] if self.layers == 3 else [])
+
+    @classmethod
+    def from_npz(cls, path: str) -> "BlockPolicy":
+        """Weights from a fixture written by tests/golden/make_block_policy_fixture.py."""
+        d = np.load(path, allow_pickle=False)
+        layers = int(d["layers"])
+        w1, wl = d["affine1_weight"], d[f"affine{layers}_weight"]
+        hidden = (w1.shape[0], d["affine2_weight"].shape[0] if layers == 3 else 0)
+        pol = cls(layers, hidden, num_actions=wl.shape[0], final_relu=bool(int(d["final_relu"])))
+        pol.load_state_dict({k: torch.from_numpy(d[k.replace(".", "_")]) for k in pol.state_dict()})
+        return pol
+
+
+def reference_block_weights(kind: str) -> Optional[str]:
+    """Path of the committed fixture of one of the reference's trained block policies
+    ("supervised3": 3 layers, no final relu; "reinforce2": 2 layers), if present."""
+    if kind not in _KINDS:
+        raise ValueError(f"kind must be one of {_KINDS}")
+    p = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(__file__))), "tests", "golden",
+                     f"block_policy_{kind}.npz")
+    return p if os.path.exists(p) else None
+
+
+def torch_block_select_action(policy: BlockPolicy, blocks: torch.Tensor, u: torch.Tensor):
+    """select_action (ball_env_reinforce.py:76-85) for a batch, fp32, with the draw
+    ``a = #{j : cdf_j <= u}`` (clamped to the last action with p > 0) from given uniforms ``u`` (N,)
+    -- the rule the HIP kernel uses.  Returns (action int64, log_prob, probs)."""
+    probs = policy(blocks.float())
+    cdf = probs.cumsum(-1)
+    a = (cdf <= u.unsqueeze(-1)).sum(-1)
+    nz = torch.arange(probs.shape[-1], device=probs.device).expand_as(probs).masked_fill(probs <= 0, 0)
+    a = torch.minimum(a, nz.max(-1).values)
+    logp = torch.log(probs.gather(-1, a.unsqueeze(-1))).squeeze(-1)
+    return a, logp, probs
+
+
+class HipBlockPolicy:
+    """``be_mlp_act`` bound to one BatchedBallEnv.
+
+    ``load(policy)`` packs the module's current fp32 weights on the device (one small kernel,
+    stream-ordered, graph-capturable) -- call it again after an optimiser step.  ``act()`` writes
+    ``action`` (N,) u8, ``log_prob`` (N,) f32 and, if ``probs=True``, ``probs`` (N, A) f32.
+    """
+
+    def __init__(self, env, policy: BlockPolicy, probs: bool = False, seed: int = 0x5E1EC7):
+        self.env = env
+        self._lib = _abi.lib()
+        self.layers, self.hidden1, self.hidden2 = policy.layers, policy.hidden1, policy.hidden2
+        self.num_actions, self.final_relu, self.seed = policy.num_actions, policy.final_relu, int(seed)
+        dev, N = env.device, env.num_envs
+        self.action = torch.zeros(N, dtype=torch.uint8, device=dev)
+        self.log_prob = torch.zeros(N, dtype=torch.float32, device=dev)
+        self.probs = torch.zeros(N, self.num_actions, dtype=torch.float32, device=dev) if probs else None
+        self._out = _abi.BeActOut(self.action.data_ptr(), self.log_prob.data_ptr(), None,
+                                  None if self.probs is None else self.probs.data_ptr())
+        h = C.c_void_p()
+        _abi.check(self._lib.be_mlp_create(env._ctx, self.layers, self.hidden1, self.hidden2, self.num_actions,
+                                           int(self.final_relu), C.byref(h)), env._ctx)
+        self._h = h
+        self._weights = None
+        self.load(policy)
+
+    def load(self, policy: BlockPolicy) -> None:
+        if (policy.layers, policy.hidden1, policy.hidden2, policy.num_actions, policy.final_relu) != \
+                (self.layers, self.hidden1, self.hidden2, self.num_actions, self.final_relu):
+            raise ValueError("policy shape does not match this HipBlockPolicy")
+        dev = self.env.device
+        ws = []
+        for lin in policy.linears():
+            ws += [lin.weight.detach().to(device=dev, dtype=torch.float32).contiguous(),
+                   lin.bias.detach().to(device=dev, dtype=torch.float32).contiguous()]
+        ptrs = [w.data_ptr() for w in ws] + [None] * (6 - len(ws))
+        _abi.check(self._lib.be_mlp_load(self._h, *ptrs, self.env._stream()), self.env._ctx)
+        self._weights = ws          # keep alive until the packing kernel has run
+
+    @property
+    def packed_bytes(self) -> int:
+        return int(self._lib.be_mlp_bytes(self._h))
+
+    def _check_rows(self, x: torch.Tensor, name: str) -> None:
+        if x.dtype != torch.uint8 or tuple(x.shape) != (self.env.num_envs, BLOCKS) or not x.is_contiguous() or \
+                x.device != self.env.device:
+            raise ValueError(f"{name} must be an (N, 29) contiguous u8 tensor on the env's device")
+
+    def act(self, blocks: Optional[torch.Tensor] = None, record: Optional[torch.Tensor] = None,
+            seed: Optional[int] = None):
+        """select_action for every env.  blocks: the (N, 29) u8 rows to run the forward on (default:
+        ``prep_state2`` of the env's current state, computed in the kernel); record: an (N, 29) u8
+        tensor that receives the rows ``env.observe_blocks()`` would return.
+        Returns (action, log_prob, probs)."""
+        if blocks is not None:
+            self._check_rows(blocks, "blocks")
+        if record is not None:
+            self._check_rows(record, "record")
+        s = self.seed if seed is None else int(seed)
+        _abi.check(self._lib.be_mlp_act(self._h, C.byref(self.env._st), None if blocks is None else blocks.data_ptr(),
+                                        None if record is None else record.data_ptr(), C.byref(self._out),
+                                        s & (2**64 - 1), self.env._stream()), self.env._ctx)
+        return self.action, self.log_prob, self.probs
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None:
+            torch.cuda.synchronize(self.env.device)
+            self._lib.be_mlp_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class BlockRollout:
+    """T steps of every env with the block policy in the loop (ball_env_reinforce.py's episode loop,
+    batched): per step ``be_mlp_act`` writes action and log_prob into row t (and, with ``record_obs``,
+    the block counts the action was drawn from into row t of ``blocks`` (T, N, 29) u8), then ``be_step``
+    writes rewards and dones into row t.  The per-step out-structs point into the (T, N) buffers, so
+    there are no copy kernels; ``capture()`` records the loop into HIP graphs (a linear chain on one
+    stream) and ``run()`` replays them."""
+
+    def __init__(self, env, policy: BlockPolicy, horizon: int, record_obs: bool = False, seed: int = 0x5E1EC7):
+        self.env, self.policy, self.T, self.seed = env, policy, int(horizon), int(seed)
+        dev, N, T = env.device, env.num_envs, self.T
+        self.actions = torch.zeros(T, N, dtype=torch.uint8, device=dev)
+        self.log_probs = torch.zeros(T, N, dtype=torch.float32, device=dev)
+        self.rewards = torch.zeros(T, N, dtype=torch.float64, device=dev)
+        self.dones = torch.zeros(T, N, dtype=torch.bool, device=dev)
+        self.blocks = torch.zeros(T, N, BLOCKS, dtype=torch.uint8, device=dev) if record_obs else None
+        self.hp = HipBlockPolicy(env, policy, seed=self.seed)
+        self._lib = _abi.lib()
+        self._graphs = []
+        self._act_outs = [_abi.BeActOut(self.actions[t].data_ptr(), self.log_probs[t].data_ptr(), None, None)
+                          for t in range(T)]
+        o = env._out
+        self._step_outs = [_abi.BeOut(o.obs, o.obs_f32, self.rewards[t].data_ptr(), self.dones[t].data_ptr(),
+                                      o.truncated, o.terminal_obs, o.final_return, o.final_len, o.stats)
+                           for t in range(T)]
+
+    def step(self, t: int, stream_ptr=None) -> None:
+        """select_action + env step of every env, results into row t."""
+        env, lib = self.env, self._lib
+        s = env._stream() if stream_ptr is None else stream_ptr
+        rec = None if self.blocks is None else self.blocks[t].data_ptr()
+        rc = lib.be_mlp_act(self.hp._h, C.byref(env._st), None, rec, C.byref(self._act_outs[t]),
+                            self.seed & (2**64 - 1), s)
+        if rc:
+            _abi.check(rc, env._ctx)
+        rc = lib.be_step(env._ctx, C.byref(env._st), C.c_void_p(self.actions[t].data_ptr()), None, None,
+                         C.byref(self._step_outs[t]), s)
+        if rc:
+            _abi.check(rc, env._ctx)
+
+    def run_eager(self) -> None:
+        for t in range(self.T):
+            self.step(t)
+
+    def capture(self, chunk: int = 250, stream: Optional[torch.cuda.Stream] = None) -> None:
+        """Record the T steps into HIP graphs of ``chunk`` steps each (stream: the stream to capture
+        on; default a new one from torch's pool)."""
+        dev = self.env.device
+        cap = torch.cuda.Stream(dev) if stream is None else stream
+        self._graphs = []
+        for c0 in range(0, self.T, max(1, int(chunk))):
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, stream=cap):
+                sp = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+                for t in range(c0, min(self.T, c0 + max(1, int(chunk)))):
+                    self.step(t, sp)
+            self._graphs.append(g)
+        torch.cuda.synchronize(dev)
+
+    def run(self) -> None:
+        """Replay the captured horizon (capture() first)."""
+        if not self._graphs:
+            raise RuntimeError("capture() first")
+        for g in self._graphs:
+            g.replay()
+
+    def close(self) -> None:
+        self._graphs = []
+        self.hp.close()
+
+
+def _episode_targets(rewards: torch.Tensor, dones: torch.Tensor, gamma: float, eps: float):
+    """(R^, valid), flat (T*N), by be_a2c_targets' rule in plain torch: the return recursion in f64,
+    R rounded to fp32 (the reference's torch.tensor(R)), then each episode's mean and unbiased std of
+    those fp32 values taken in f64 and R^ rounded once to fp32."""
+    T, N = rewards.shape
+    dev = rewards.device
+    d64 = dones.to(torch.float64)
+    R = torch.empty(T, N, dtype=torch.float64, device=dev)
+    acc = torch.zeros(N, dtype=torch.float64, device=dev)
+    for t in range(T - 1, -1, -1):
+        acc = rewards[t].to(torch.float64) + gamma * acc * (1.0 - d64[t])
+        R[t] = acc
+    flat = R.to(torch.float32).to(torch.float64).reshape(-1)
+    # episode id of every (t, env): dones strictly before t in that env, then env
+    seg = (torch.cumsum(dones.to(torch.int64), 0) - dones.to(torch.int64)) * N + torch.arange(N, device=dev)
+    _, sid = torch.unique(seg.reshape(-1), return_inverse=True)
+    S = int(sid.max()) + 1
+    cnt = torch.bincount(sid, minlength=S).to(torch.float64)
+    mean = torch.zeros(S, dtype=torch.float64, device=dev).index_add_(0, sid, flat) / cnt
+    var = torch.zeros(S, dtype=torch.float64, device=dev).index_add_(0, sid, (flat - mean[sid]) ** 2) / \
+        (cnt - 1).clamp(min=1)
+    Rn = ((flat - mean[sid]) / (var.sqrt()[sid] + eps)).to(torch.float32)
+    return Rn, (cnt > 1)[sid]
+
+
+def reinforce_losses(policy: BlockPolicy, blocks: torch.Tensor, actions: torch.Tensor, rewards: torch.Tensor,
+                     dones: torch.Tensor, gamma: float = 0.99, targets=None) -> torch.Tensor:
+    """Batched ``finish_episode`` (examples/ball_env_reinforce.py:88-108) over a recorded rollout.
+
+    blocks (T, N, 29) u8 -- the rows each action was drawn from; actions (T, N); rewards (T, N) f64;
+    dones (T, N) bool.  Every maximal run of an env's steps that ends at a done (or at the horizon)
+    is one episode, as ``policy.rewards`` / ``policy.saved_log_probs`` are in the reference.  Per
+    episode, as there: R_t = r_t + gamma R_{t+1}, then torch.tensor(R) (fp32),
+    R^ = (R - R.mean()) / (R.std() + eps) (unbiased std, eps = fp32 eps), loss = sum_t -log pi(a_t|s_t) R^_t.
+    Episodes of one step are left out (the reference's std() of one element is NaN).  log pi is
+    recomputed from ``blocks`` with autograd, as ``Categorical(probs).log_prob``.  Returns the loss summed over all episodes (f64).
+
+    targets: ``(returns_norm, valid)``, both (T, N) -- R^ and the "episode has >= 2 steps" mask from
+    ``a2c_targets(env, rewards, dones, None, gamma)`` (one HIP kernel, the same normalisation)."""
+    T, N = rewards.shape
+    if targets is None:
+        Rn, valid = _episode_targets(rewards, dones, gamma, float(np.finfo(np.float32).eps))
+    else:
+        Rn, valid = targets[0], targets[1]
+        if tuple(Rn.shape) != (T, N) or tuple(valid.shape) != (T, N):
+            raise ValueError("targets must be (returns_norm, valid), both (T, N)")
+        Rn, valid = Rn.reshape(-1), valid.reshape(-1).to(torch.bool)
+    probs = policy(blocks.reshape(T * N, BLOCKS).float())
+    # the reference's m.log_prob(action): Categorical renormalises the probabilities and clamps them to
+    # [eps, 1 - eps] before the log, so an action of probability ~0 has a finite loss and no gradient
+    logp = torch.distributions.Categorical(probs=probs).log_prob(actions.reshape(-1).long())
+    return -(logp.double() * Rn.double())[valid].sum()      # products and sum in f64: no rounding of its own
+
+
+def reinforce_update(rollout: BlockRollout, optimizer, gamma: float = 0.99, targets: str = "hip") -> float:
+    """One REINFORCE step on a recorded rollout (record_obs=True): the targets (targets="hip":
+    ``be_a2c_targets`` with no values; "torch": ``reinforce_losses``' own), loss.backward(),
+    optimizer.step(), then the new weights re-packed for the HIP kernel.  Returns the loss value."""
+    if rollout.blocks is None:
+        raise ValueError("reinforce_update needs BlockRollout(record_obs=True)")
+    if targets not in ("torch", "hip"):
+        raise ValueError("targets must be 'torch' or 'hip'")
+    tg = None
+    if targets == "hip":
+        from .rollout import a2c_targets
+        t = a2c_targets(rollout.env, rollout.rewards, rollout.dones, None, gamma, with_returns=False)
+        tg = (t.returns_norm, t.valid)
+    loss = reinforce_losses(rollout.policy, rollout.blocks, rollout.actions, rollout.rewards, rollout.dones, gamma,
+                            targets=tg)
+    optimizer.zero_grad()
+    loss.backward()
+    optimizer.step()
+    rollout.hp.load(rollout.policy)
+    return float(loss.detach())

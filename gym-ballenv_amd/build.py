@@ -21,6 +21,8 @@ object) and linked into one shared library:
                     instance measured 14 % slower, W = 5 the same: profiles/a2c_grad_ab.json)
   csrc/a2c_adam.hip the Adam step on the six Policy tensors and the re-pack of the policy image (f64
                     operations with -ffp-contract=off, as every unit: the pinned arithmetic has no FMA)
+  csrc/mlp_policy.hip select_action of the REINFORCE / supervised block-count MLP (f32 MFMAs) straight
+                    from the env state; shares blocks_core.h (prep_state2 of one env) with features.hip
 """
 from __future__ import annotations
 
@@ -46,8 +48,9 @@ VGPR_MFMA = ["-mllvm", "-amdgpu-mfma-vgpr-form"]
 # prologue); the compiler keeps an s_load entry for firmware without the preload.
 KARG_PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
 UNITS = {"ballenv.hip": [*VGPR_MFMA, *KARG_PRELOAD], "abi.hip": [], "policy.hip": ["-fno-slp-vectorize", *VGPR_MFMA],
-         "features.hip": [], "board.hip": [], "a2c.hip": [], "a2c_grad.hip": [], "a2c_adam.hip": []}
-HEADERS = [HDR, *(os.path.join(CSRC, h) for h in ("philox.h", "internal.h", "host_logic.h", "pool_layout.h", "policy_core.h", "diag.h",
+         "features.hip": [], "board.hip": [], "a2c.hip": [], "a2c_grad.hip": [], "a2c_adam.hip": [],
+         "mlp_policy.hip": []}
+HEADERS = [HDR, *(os.path.join(CSRC, h) for h in ("philox.h", "internal.h", "host_logic.h", "pool_layout.h", "policy_core.h", "blocks_core.h", "diag.h",
                                               "step_types.h"))]
 
 

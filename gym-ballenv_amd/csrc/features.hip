@@ -22,13 +22,10 @@
 #include <stdio.h>
 
 #include "ballenv.h"
+#include "blocks_core.h"
 #include "internal.h"
 
 namespace {
-
-__device__ __forceinline__ int floordiv20(int a) { return a >= 0 ? a / 20 : -((-a + 19) / 20); }
-__device__ __forceinline__ int px(int32_t p) { return (int)(int16_t)(p & 0xFFFF); }
-__device__ __forceinline__ int py(int32_t p) { return p >> 16; }
 
 struct BParams {
   const int32_t* agent; const int32_t* goal; const int32_t* static_obs; const int32_t* dyn_obs;
@@ -56,7 +53,7 @@ __device__ __forceinline__ void copy_chunks(const uint8_t* stage, uint8_t* dst, 
   for (int j = 0; j < IT; ++j) __builtin_amdgcn_raw_buffer_store_b128(x[j], rsrc, (lane + 64 * j) * 16, 0, BLOCKS_AUX);
 }
 
-constexpr int BLK_ROW = 29, BLK_WAVE_U8 = 64 * BLK_ROW, BLK_WAVE_F32 = 64 * BLK_ROW * 4;
+constexpr int BLK_WAVE_U8 = 64 * BLK_ROW, BLK_WAVE_F32 = 64 * BLK_ROW * 4;
 
 // dynamic LDS: 4 wave stages of BLK_WAVE_U8 bytes, or BLK_WAVE_F32 when f32 rows are asked for (a
 // u8-only launch keeps 7.4 KB per block, so LDS does not cap the waves per CU)
@@ -69,10 +66,9 @@ __global__ __launch_bounds__(256) void blocks_kernel(BParams p) {
   const bool valid = i < p.n;
   const int ic = valid ? i : p.n - 1;
   const int32_t a = p.agent[ic], gl = p.goal[ic];
-  const int ax = px(a), ay = py(a), dx = px(gl) - ax, dy = py(gl) - ay;
-  uint32_t w8[8] = {0, 0, 0, 0, 1u, 0, 0, 0};     // byte 16 (the agent's cell) = 1
-  const int quad = dx >= 0 ? (dy >= 0 ? 1 : 2) : (dy >= 0 ? 0 : 3);
-  w8[0] = 1u << (8 * quad);
+  const int ax = px(a), ay = py(a);
+  uint32_t w8[BLK_WORDS];
+  blocks_init(w8, a, gl);
   // obstacles in chunks of CH: every load of a chunk is issued before the first is used (clamped to
   // a real obstacle, the extra slots masked), so a wave waits for memory once per chunk instead of
   // once per pair of obstacles
@@ -87,17 +83,7 @@ __global__ __launch_bounds__(256) void blocks_kernel(BParams p) {
       o[j] = src[ic];
     }
 #pragma unroll
-    for (int j = 0; j < CH; ++j) {
-      const int xd = ax - px(o[j]), yd = ay - py(o[j]);
-      const bool off = xd == 0 || yd == 0;   // the reference's sign(0) = 0: block 0 on both axes
-      const int xb = off ? 0 : floordiv20(xd > 0 ? xd - 10 : 10 - xd);
-      const int yb = off ? 0 : floordiv20(yd > 0 ? yd - 10 : 10 - yd);
-      const bool in = k0 + j < nobs && xb > -3 && xb < 3 && yb > -3 && yb < 3;
-      const int cell = 16 + 5 * yb + xb;         // byte index 4 + (12 + 5 yb + xb)
-      const uint32_t inc = in ? 1u << (8 * (cell & 3)) : 0u;
-#pragma unroll
-      for (int q = 1; q < 8; ++q) w8[q] += (cell >> 2) == q ? inc : 0u;
-    }
+    for (int j = 0; j < CH; ++j) blocks_add(w8, ax, ay, o[j], k0 + j < nobs);
   }
   uint8_t* stage = smem + w * (p.out_f32 ? BLK_WAVE_F32 : BLK_WAVE_U8);
   const bool full = nrows == 64;

@@ -1,0 +1,410 @@
+// mlp_policy.hip -- on-GPU select_action of the reference's REINFORCE / supervised agents
+// (DESIGN §3.14): the block-count MLP on the 29-wide prep_state2 observation, straight from the
+// env state, plus the Categorical draw -- one launch for every env.
+//
+// Reference:
+//   examples/ball_env_reinforce.py:57-85   Policy (affine1 29->128, affine2, affine3 -> 9; relu on
+//                                          every layer, the last included :70) and select_action
+//   examples/test_model.py:57-85           the same network, evaluated
+//   examples/train_supervise.py:11-26      Model: the same layers, no relu on the last
+//   examples/ball_env_reinforce.py:130-172 prep_state2, the input (blocks_core.h)
+//
+//   be_mlp_load   one launch: the f32 state_dict arrays into the padded image the kernel stages
+//   be_mlp_act    one launch: [prep_state2 ->] forward -> softmax -> draw, the arithmetic
+//                 include/ballenv.h pins
+//
+// Every product runs on v_mfma_f32_16x16x4_f32 (an exact f32 fma chain) as D = W . x^T: the
+// weights are the A operand (row = output unit), a tile of 16 envs the B operand (column = env),
+// so lane (c = lane & 15, g = lane >> 4) ends a layer holding units 16 t + 4 g + r (r = 0..3) of
+// env c in accumulator t.  Those registers ARE the next layer's B operand: a k step of an MFMA
+// may take the inputs in any order as long as A and B agree, so step (t, r) of the next layer
+// multiplies the weight columns 16 t + 4 g + r, which is how be_mlp_load lays the A fragments
+// out.  No activation goes through LDS, and no product has a shape test: hidden sizes are padded
+// to the instance's 128 and the actions to 16 with zero weights and biases (relu(0) = 0 adds
+// nothing), the 29 inputs to 32.
+//
+// A persistent grid, one workgroup of 8 waves per CU; the image (89 KB in f32 at 128/128/9) is staged
+// once per workgroup in LDS, fragment-major (one conflict-free 4-byte read per lane and MFMA), then
+// wave w of workgroup b of G takes the 16-env tiles b + G w, + 8 G, ... with no block barrier (a batch
+// of up to 16 G envs runs one wave per CU: the 4-wave build's time at 4 096 envs).  Per tile:
+//   1  prep_state2 of the 16 envs: lane group g takes obstacles g, g + 4, ..., the four partial rows
+//      are summed with permlane swaps (byte counters cannot carry); or the caller's rows
+//   2  the layers, the bias in the accumulator's start
+//   3  the 16 logits of each env through the wave's LDS slice to lanes 0..15: softmax, draw,
+//      log_prob (policy_core.h's policy_finish, the tail of be_policy_act)
+#include <hip/hip_runtime.h>
+
+#include <math.h>
+#include <new>
+#include <stdint.h>
+
+#include "ballenv.h"
+#include "blocks_core.h"
+#include "internal.h"
+#include "philox.h"
+#include "policy_core.h"
+
+namespace {
+
+#ifndef BE_MLP_WAVES
+#define BE_MLP_WAVES 8       // -DBE_MLP_WAVES=n: timing builds with n waves per workgroup
+#endif
+constexpr int MLP_NW = BE_MLP_WAVES, MLP_THREADS = 64 * MLP_NW;
+constexpr int MLP_TILE = 16;                 // envs per wave and tile
+constexpr int MLP_MAXH = 128, MLP_KS1 = 8;   // 4-wide k steps of layer 1 (29 -> 32 inputs)
+constexpr int MLP_NO = 16;                   // padded outputs: policy_finish<16> (actions 0..14, slot 15 unused)
+constexpr int MLP_ZP = 17;                   // row stride of a tile's logits in the wave's slice
+constexpr int MLP_SLICE = 16 * MLP_ZP + 16 * BLK_ROW / 4 + 12;   // floats per wave: logits, then 16 rows of blocks
+constexpr int MLP_CH = 5;                    // obstacles per lane and load chunk (4 groups: 20 per pass)
+static_assert(MLP_SLICE % 4 == 0 && 16 * BLK_ROW % 4 == 0, "the slices stay 16-byte aligned");
+static_assert(POL_MAXA < MLP_NO, "policy_finish<16> holds be_policy_create's action bound");
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// The packed image, identical in HBM and in each workgroup's LDS (offsets in floats).  HT1 / HT2 / HTL
+// are 16-row tiles of hidden1 / hidden2 / the last layer's input; l15 = lane & 15, l4 = lane >> 4.
+struct MlpLayout {
+  int layers, HT1, HT2, HTL;
+  int f1;      // [MLP_KS1][HT1][64]   W1[16 t + l15][4 k + l4]
+  int b1;      // [16 HT1]
+  int f2;      // [4 HT1][HT2][64]     W2[16 t + l15][16 (s >> 2) + 4 l4 + (s & 3)]     (3 layers)
+  int b2;      // [16 HT2]                                                               (3 layers)
+  int f3;      // [4 HTL][64]          W_last[l15][16 (s >> 2) + 4 l4 + (s & 3)]
+  int b3;      // [16]
+  int hb;      // [16]                 0 for an action (and slot 15), -inf for a pad action
+  int total, lds;                      // floats of the image; bytes of LDS with the waves' slices
+};
+__host__ __device__ constexpr MlpLayout mlp_layout(int layers, int HT1, int HT2) {
+  MlpLayout L{};
+  L.layers = layers; L.HT1 = HT1; L.HT2 = layers == 3 ? HT2 : 0; L.HTL = layers == 3 ? HT2 : HT1;
+  L.f1 = 0;
+  L.b1 = L.f1 + MLP_KS1 * HT1 * 64;
+  L.f2 = L.b1 + 16 * HT1;
+  L.b2 = L.f2 + 4 * HT1 * L.HT2 * 64;
+  L.f3 = L.b2 + 16 * L.HT2;
+  L.b3 = L.f3 + 4 * L.HTL * 64;
+  L.hb = L.b3 + 16;
+  L.total = L.hb + 16;
+  L.lds = (L.total + MLP_NW * MLP_SLICE) * 4;
+  return L;
+}
+
+struct MPack {               // device f32 weights in torch state_dict layout; wl / bl: the last layer
+  const float *w1, *b1, *w2, *b2, *wl, *bl;
+  int H1, H2, A;
+};
+
+__global__ __launch_bounds__(256) void mlp_pack_kernel(MPack a, float* img, MlpLayout L) {
+  const int HL = L.layers == 3 ? a.H2 : a.H1;
+  for (int i = (int)(blockIdx.x * 256 + threadIdx.x); i < L.total; i += (int)gridDim.x * 256) {
+    float v = 0.0f;
+    if (i < L.b1) {
+      const int lane = i & 63, t = i >> 6, ht = t % L.HT1, kk = t / L.HT1;
+      const int m = 16 * ht + (lane & 15), k = 4 * kk + (lane >> 4);
+      if (m < a.H1 && k < BLK_ROW) v = a.w1[m * BLK_ROW + k];
+    } else if (i < L.f2) {
+      const int m = i - L.b1;
+      if (m < a.H1) v = a.b1[m];
+    } else if (i < L.b2) {
+      const int j = i - L.f2, lane = j & 63, t = j >> 6, mt = t % L.HT2, s = t / L.HT2;
+      const int m = 16 * mt + (lane & 15), k = 16 * (s >> 2) + 4 * (lane >> 4) + (s & 3);
+      if (m < a.H2 && k < a.H1) v = a.w2[m * a.H1 + k];
+    } else if (i < L.f3) {
+      const int m = i - L.b2;
+      if (m < a.H2) v = a.b2[m];
+    } else if (i < L.b3) {
+      const int j = i - L.f3, lane = j & 63, s = j >> 6;
+      const int m = lane & 15, k = 16 * (s >> 2) + 4 * (lane >> 4) + (s & 3);
+      if (m < a.A && k < HL) v = a.wl[m * HL + k];
+    } else if (i < L.hb) {
+      const int m = i - L.b3;
+      if (m < a.A) v = a.bl[m];
+    } else {
+      const int m = i - L.hb;
+      v = (m < a.A || m == MLP_NO - 1) ? 0.0f : -INFINITY;
+    }
+    img[i] = v;
+  }
+}
+
+struct MParams {
+  const float* img;
+  const int32_t* agent; const int32_t* goal; const int32_t* static_obs; const int32_t* dyn_obs;
+  const uint32_t* episode;   // (N) Philox key words (be_state.episode / ep_len)
+  const int32_t* ep_len;
+  const uint8_t* blocks_in;  // (N, 29) or NULL: prep_state2 of the state
+  uint8_t* blocks_out;       // (N, 29) or NULL
+  uint8_t* action;           // (N)
+  float* log_prob;           // (N) or NULL
+  float* probs;              // (N, A) or NULL
+  unsigned long long seed;
+  int32_t n, ns, nd, ntiles, A, gid0, final_relu;
+};
+
+// sum of x over lanes l, l^16, l^32, l^48 (or_groups of policy_core.h with +)
+__device__ __forceinline__ uint32_t sum_groups_u32(uint32_t x) {
+  const auto a = __builtin_amdgcn_permlane16_swap(x, x, false, false);
+  x = a[0] + a[1];
+  const auto b = __builtin_amdgcn_permlane32_swap(x, x, false, false);
+  return b[0] + b[1];
+}
+
+// wave barrier between a slice's writes and its reads by other lanes of the wave
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+#define BE_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
+
+// One layer with HTI input tiles (h, relu'd, in the accumulator layout) and HTO output tiles:
+// acc[t] starts at the bias.  frag: [4 HTI][HTO][64], bias: [16 HTO].
+template <int HTI, int HTO>
+__device__ __forceinline__ void mlp_hidden(const float* frag, const float* bias, const f32x4 (&h)[HTI], int lane,
+                                           f32x4 (&acc)[HTO]) {
+#pragma unroll
+  for (int t = 0; t < HTO; ++t) acc[t] = *(const f32x4*)(bias + 16 * t + 4 * (lane >> 4));
+#pragma unroll
+  for (int hp = 0; hp < HTI; ++hp)
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int t = 0; t < HTO; ++t) acc[t] = BE_MFMA(frag[((hp * 4 + r) * HTO + t) * 64 + lane], h[hp][r], acc[t]);
+#pragma unroll
+  for (int t = 0; t < HTO; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc[t][r] = fmaxf(acc[t][r], 0.0f);
+}
+
+// The last layer: one output tile, four fma chains (chain r takes the steps (t, r); chain 0 starts at
+// the bias), z = (c0 + c1) + (c2 + c3).
+template <int HTI>
+__device__ __forceinline__ f32x4 mlp_last(const float* frag, const float* bias, const f32x4 (&h)[HTI], int lane) {
+  const f32x4 zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
+  f32x4 c[4] = {*(const f32x4*)(bias + 4 * (lane >> 4)), zero4, zero4, zero4};
+#pragma unroll
+  for (int hp = 0; hp < HTI; ++hp)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) c[r] = BE_MFMA(frag[(hp * 4 + r) * 64 + lane], h[hp][r], c[r]);
+  return (c[0] + c[1]) + (c[2] + c[3]);
+}
+
+template <int LAYERS, int HT1, int HT2>
+__global__ __launch_bounds__(MLP_THREADS) void mlp_act_kernel(MParams p) {
+  extern __shared__ uint4 mlp_lds[];
+  constexpr MlpLayout L = mlp_layout(LAYERS, HT1, HT2);
+  static_assert(L.total % 4 == 0, "the image is staged in 16-byte words");
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l15 = lane & 15, l4 = lane >> 4;
+  stage_image<MLP_THREADS, 6>(mlp_lds, (const uint4*)p.img, L.total / 4, tid);
+  __syncthreads();
+  const float* W = (const float*)mlp_lds;
+  float* Zs = (float*)mlp_lds + L.total + wave * MLP_SLICE;
+  uint8_t* rows = (uint8_t*)(Zs + 16 * MLP_ZP);
+  const bool from_state = p.blocks_in == nullptr;
+  const int nobs = p.ns + p.nd;
+
+  for (int tile = (int)blockIdx.x + (int)gridDim.x * wave; tile < p.ntiles; tile += (int)gridDim.x * MLP_NW) {
+    const int e0 = tile * MLP_TILE, env = e0 + l15;
+    const int ic = env < p.n ? env : p.n - 1;     // a clamped env computes and writes nothing
+    // the draw's Philox key words (lane c < 16 finishes env e0 + c)
+    const uint32_t episode = lane < 16 ? p.episode[ic] : 0u;
+    const int32_t len = lane < 16 ? p.ep_len[ic] : 0;
+
+    // 1: the B operand of layer 1: x[k] = input 4 k + l4 of env l15
+    float x[MLP_KS1];
+    if (from_state || p.blocks_out) {
+      const int32_t a = p.agent[ic], gl = p.goal[ic];
+      const int ax = px(a), ay = py(a);
+      uint32_t w8[BLK_WORDS];
+      blocks_init(w8, a, gl);
+#pragma unroll
+      for (int q = 0; q < BLK_WORDS; ++q) w8[q] = l4 == 0 ? w8[q] : 0u;
+      // every load of a chunk is issued before the first is used (clamped to a real obstacle, the
+      // extra slots masked), as in blocks_kernel
+      for (int k0 = 0; k0 < nobs; k0 += 4 * MLP_CH) {
+        int32_t o[MLP_CH];
+#pragma unroll
+        for (int j = 0; j < MLP_CH; ++j) {
+          const int k = min(k0 + 4 * j + l4, nobs - 1);
+          const int32_t* src = k < p.ns ? p.static_obs + (int64_t)k * p.n : p.dyn_obs + (int64_t)(k - p.ns) * p.n;
+          o[j] = src[ic];
+        }
+#pragma unroll
+        for (int j = 0; j < MLP_CH; ++j) blocks_add(w8, ax, ay, o[j], k0 + 4 * j + l4 < nobs);
+      }
+#pragma unroll
+      for (int q = 0; q < BLK_WORDS; ++q) w8[q] = sum_groups_u32(w8[q]);
+      if (p.blocks_out) {      // the tile's rows are one contiguous run of the output
+        // lane group g writes bytes 8 g .. 8 g + 7 of its env's row: words 2 g and 2 g + 1, picked with
+        // selects (an indexed w8 would live in scratch memory); group 3 ends at byte 28
+        const uint32_t lo = l4 == 0 ? w8[0] : (l4 == 1 ? w8[2] : (l4 == 2 ? w8[4] : w8[6]));
+        const uint32_t hi = l4 == 0 ? w8[1] : (l4 == 1 ? w8[3] : (l4 == 2 ? w8[5] : w8[7]));
+        uint8_t* rb = rows + l15 * BLK_ROW + 8 * l4;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) rb[j] = (uint8_t)(lo >> (8 * j));
+        rb[4] = (uint8_t)hi;
+        if (l4 < 3) {
+#pragma unroll
+          for (int j = 1; j < 4; ++j) rb[4 + j] = (uint8_t)(hi >> (8 * j));
+        }
+        wave_sync();
+        const int nbytes = min(MLP_TILE, p.n - e0) * BLK_ROW;
+        uint8_t* dst = p.blocks_out + (int64_t)e0 * BLK_ROW;
+        for (int b = lane; b < nbytes; b += 64) dst[b] = rows[b];
+        wave_sync();
+      }
+#pragma unroll
+      for (int k = 0; k < MLP_KS1; ++k) x[k] = (float)((w8[k] >> (8 * l4)) & 0xFFu);
+    }
+    if (!from_state) {
+      const uint8_t* row = p.blocks_in + (int64_t)ic * BLK_ROW;
+#pragma unroll
+      for (int k = 0; k < MLP_KS1; ++k) {
+        const int col = 4 * k + l4;
+        const uint8_t v = row[min(col, BLK_ROW - 1)];
+        x[k] = col < BLK_ROW ? (float)v : 0.0f;
+      }
+    }
+
+    // 2: the layers
+    f32x4 h1[HT1];
+#pragma unroll
+    for (int t = 0; t < HT1; ++t) h1[t] = *(const f32x4*)(W + L.b1 + 16 * t + 4 * l4);
+#pragma unroll
+    for (int k = 0; k < MLP_KS1; ++k)
+#pragma unroll
+      for (int t = 0; t < HT1; ++t) h1[t] = BE_MFMA(W[L.f1 + (k * HT1 + t) * 64 + lane], x[k], h1[t]);
+#pragma unroll
+    for (int t = 0; t < HT1; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) h1[t][r] = fmaxf(h1[t][r], 0.0f);
+    f32x4 z;
+    if constexpr (LAYERS == 3) {
+      f32x4 h2[HT2];
+      mlp_hidden<HT1, HT2>(W + L.f2, W + L.b2, h1, lane, h2);
+      z = mlp_last<HT2>(W + L.f3, W + L.b3, h2, lane);
+    } else {
+      z = mlp_last<HT1>(W + L.f3, W + L.b3, h1, lane);
+    }
+
+    // 3: logits 4 l4 + r of env l15 -> the slice; lane c < 16 finishes env e0 + c
+#pragma unroll
+    for (int r = 0; r < 4; ++r) Zs[l15 * MLP_ZP + 4 * l4 + r] = p.final_relu ? fmaxf(z[r], 0.0f) : z[r];
+    wave_sync();
+    if (lane < 16 && env < p.n) {
+      float lp, val;
+      const int act = policy_finish<MLP_NO>(Zs + lane * MLP_ZP, W + L.hb, p.A, (uint32_t)(p.gid0 + env), episode,
+                                            (uint32_t)len, p.seed, p.probs ? p.probs + (int64_t)env * p.A : nullptr,
+                                            lp, val);
+      p.action[env] = (uint8_t)act;
+      if (p.log_prob) p.log_prob[env] = lp;
+    }
+    wave_sync();
+  }
+}
+
+// Every shape runs the instance of its layer count, padded to 128 hidden units.
+constexpr int MLP_HT = MLP_MAXH / 16;
+
+}  // namespace
+
+struct be_mlp {
+  be_ctx* ctx;
+  be_ctx_view cv;
+  int layers, H1, H2, A, final_relu, cus;
+  MlpLayout L;
+  float* img;
+  bool loaded;
+};
+
+extern "C" {
+
+int be_mlp_create(be_ctx* ctx, int32_t layers, int32_t hidden1, int32_t hidden2, int32_t num_actions,
+                  int32_t final_relu, be_mlp** out) {
+  if (!ctx || !out) return be_ctx_fail(ctx, BE_E_INVALID, "bad arguments to be_mlp_create");
+  *out = nullptr;
+  if (layers != 2 && layers != 3) return be_ctx_fail(ctx, BE_E_INVALID, "be_mlp_create: layers must be 2 or 3");
+  if (hidden1 < 1 || hidden1 > MLP_MAXH) return be_ctx_fail(ctx, BE_E_INVALID, "be_mlp_create: hidden1 must be in [1, 128]");
+  if (layers == 3 && (hidden2 < 1 || hidden2 > MLP_MAXH))
+    return be_ctx_fail(ctx, BE_E_INVALID, "be_mlp_create: hidden2 must be in [1, 128]");
+  if (layers == 2 && hidden2 != 0) return be_ctx_fail(ctx, BE_E_INVALID, "be_mlp_create: hidden2 must be 0 with 2 layers");
+  if (num_actions < 1 || num_actions > POL_MAXA)
+    return be_ctx_fail(ctx, BE_E_INVALID, "be_mlp_create: num_actions must be in [1, 15]");
+  be_mlp* m = new (std::nothrow) be_mlp();
+  if (!m) return be_ctx_fail(ctx, BE_E_NOMEM, "out of host memory");
+  m->ctx = ctx; m->cv = be_ctx_get(ctx);
+  m->layers = layers; m->H1 = hidden1; m->H2 = hidden2; m->A = num_actions; m->final_relu = final_relu ? 1 : 0;
+  m->L = mlp_layout(layers, MLP_HT, MLP_HT);
+  const DeviceGuard dg(m->cv.device);   // the caller's current device is restored on return
+  hipError_t e = dg.err;
+  if (e == hipSuccess) e = hipDeviceGetAttribute(&m->cus, hipDeviceAttributeMultiprocessorCount, m->cv.device);
+  if (e == hipSuccess) e = hipMalloc(&m->img, (size_t)m->L.total * 4);
+  if (e == hipSuccess) e = hipMemset(m->img, 0, (size_t)m->L.total * 4);
+  if (e != hipSuccess || m->cus < 1) {
+    if (m->img) (void)hipFree(m->img);
+    delete m;
+    if (e == hipSuccess) return be_ctx_fail(ctx, BE_E_HIP, "be_mlp_create: cannot query the device's compute units");
+    return be_hip_fail(be_ctx_err(ctx), e);
+  }
+  *out = m;
+  return BE_OK;
+}
+
+int be_mlp_destroy(be_mlp* m) {
+  if (!m) return BE_OK;
+  const DeviceGuard dg(m->cv.device);
+  if (m->img) (void)hipFree(m->img);
+  delete m;
+  return BE_OK;
+}
+
+int be_mlp_load(be_mlp* m, const float* w1, const float* b1, const float* w2, const float* b2, const float* w3,
+                const float* b3, void* stream) {
+  if (!m) return be_ctx_fail(nullptr, BE_E_INVALID, "be_mlp_load: mlp is NULL");
+  be_ctx* ctx = m->ctx;
+  if (!w1 || !b1 || !w2 || !b2) return be_ctx_fail(ctx, BE_E_INVALID, "be_mlp_load: a weight pointer is NULL");
+  if (m->layers == 3 && (!w3 || !b3)) return be_ctx_fail(ctx, BE_E_INVALID, "be_mlp_load: 3 layers need w3 and b3");
+  if (m->layers == 2 && (w3 || b3)) return be_ctx_fail(ctx, BE_E_INVALID, "be_mlp_load: w3 and b3 must be NULL with 2 layers");
+  BE_ENTER_DEVICE(be_ctx_err(ctx), m->cv.device);
+  const MPack a = m->layers == 3 ? MPack{w1, b1, w2, b2, w3, b3, m->H1, m->H2, m->A}
+                                 : MPack{w1, b1, nullptr, nullptr, w2, b2, m->H1, 0, m->A};
+  hipLaunchKernelGGL(mlp_pack_kernel, dim3((unsigned)((m->L.total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a,
+                     m->img, m->L);
+  if (int rc = be_launched(be_ctx_err(ctx))) return rc;
+  m->loaded = true;
+  return BE_OK;
+}
+
+int be_mlp_act(be_mlp* m, const be_state* st, const uint8_t* blocks_in, uint8_t* blocks_out, const be_act_out* out,
+               uint64_t seed, void* stream) {
+  if (!m) return be_ctx_fail(nullptr, BE_E_INVALID, "be_mlp_act: mlp is NULL");
+  be_ctx* ctx = m->ctx;
+  if (!m->loaded) return be_ctx_fail(ctx, BE_E_INVALID, "be_mlp_act before be_mlp_load");
+  if (int rc = be_ctx_check_state(ctx, st)) return rc;
+  if (!out || !out->action) return be_ctx_fail(ctx, BE_E_INVALID, "be_mlp_act needs out->action");
+  if (out->value) return be_ctx_fail(ctx, BE_E_INVALID, "be_mlp_act: out->value must be NULL (this network has no value head)");
+  BE_ENTER_DEVICE(be_ctx_err(ctx), m->cv.device);
+  MParams p{};
+  p.img = m->img;
+  p.agent = st->agent; p.goal = st->goal; p.static_obs = st->static_obs; p.dyn_obs = st->dyn_obs;
+  p.episode = st->episode; p.ep_len = st->ep_len;
+  p.blocks_in = blocks_in; p.blocks_out = blocks_out;
+  p.action = out->action; p.log_prob = out->log_prob; p.probs = out->probs;
+  p.seed = (unsigned long long)seed;
+  p.n = m->cv.num_envs; p.ns = m->cv.num_static; p.nd = m->cv.num_dynamic;
+  p.ntiles = (p.n + MLP_TILE - 1) / MLP_TILE;
+  p.A = m->A; p.gid0 = (int32_t)(uint32_t)m->cv.env_offset; p.final_relu = m->final_relu;
+  // tiles go to the workgroups first, then to their waves: a small batch runs one wave on every CU
+  const dim3 grid((unsigned)(p.ntiles < m->cus ? p.ntiles : m->cus)), block(MLP_THREADS);
+  if (m->layers == 3)
+    hipLaunchKernelGGL((mlp_act_kernel<3, MLP_HT, MLP_HT>), grid, block, (size_t)m->L.lds, (hipStream_t)stream, p);
+  else
+    hipLaunchKernelGGL((mlp_act_kernel<2, MLP_HT, 0>), grid, block, (size_t)m->L.lds, (hipStream_t)stream, p);
+  return be_launched(be_ctx_err(ctx));
+}
+
+int64_t be_mlp_bytes(const be_mlp* m) { return m ? (int64_t)m->L.total * 4 : 0; }
+
+}  // extern "C"

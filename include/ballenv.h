@@ -323,6 +323,43 @@ int64_t be_policy_bytes(const be_policy* pol);
  * in its 20-px block of the 5x5 grid -- as u8 (out) and/or f32 (out_f32; NULL = skip). */
 int be_observe_blocks(be_ctx* ctx, const be_state* st, uint8_t* out, float* out_f32, void* stream);
 
+/* ---- on-GPU select_action of the REINFORCE / supervised agents (the block-count MLP) ----
+ * Replaces, for every env at once, the caller's per-step
+ *   probs = Policy()(prep_state2(state))                examples/ball_env_reinforce.py:57-73, 130-172
+ *   action ~ Categorical(probs); saved log_prob          ball_env_reinforce.py:76-85
+ * (also examples/test_model.py:57-85, and the Model of examples/train_supervise.py:11-26, whose
+ * last layer has no relu).  The network: affine1 (29 -> hidden1), relu, [affine2 (hidden1 ->
+ * hidden2), relu,] last layer (-> num_actions), [relu,] softmax.  It has no value head.
+ * The arithmetic is pinned (csrc/mlp_policy.hip has the operand order of the fma chains):
+ *   x      = the 29 u8 counts as f32 (exact: a count is at most 19 in the default config)
+ *   h1     = relu(W1 x + b1);   3 layers: h2 = relu(W2 h1 + b2)
+ *   z      = W_last h + b_last;  z = relu(z) iff final_relu
+ *   p      = softmax(z), max-subtracted, as be_policy_act's
+ *   a      = #{j : cdf_j <= u}, clamped to the last action with p > 0;  log_prob = log p[a]
+ *   u      = the uniform be_policy_act draws: Philox(seed; global env id, episode, ep_len, POLICY)
+ * Every product is an f32 fma chain on v_mfma_f32_16x16x4_f32 that starts at the bias.
+ * layers 2 | 3; hidden1, hidden2 in [1, 128] (hidden2 = 0 with 2 layers); num_actions in [1, 15]. */
+typedef struct be_mlp be_mlp;
+int be_mlp_create(be_ctx* ctx, int32_t layers, int32_t hidden1, int32_t hidden2, int32_t num_actions,
+                  int32_t final_relu, be_mlp** out);
+int be_mlp_destroy(be_mlp* mlp);
+/* (Re)load weights from DEVICE f32 arrays in torch state_dict layout: w1 (hidden1, 29), b1 (hidden1);
+ * 3 layers: w2 (hidden2, hidden1), b2, w3 (A, hidden2), b3 (A); 2 layers: w2 (A, hidden1), b2 (A),
+ * w3 = b3 = NULL.  One packing kernel into the padded image be_mlp_act stages (K 29 -> 32, hidden
+ * -> 128, actions -> 16; pad rows and columns are zero).  Asynchronous on stream, graph-capturable,
+ * allocates nothing.                                                                            */
+int be_mlp_load(be_mlp* mlp, const float* w1, const float* b1, const float* w2, const float* b2, const float* w3,
+                const float* b3, void* stream);
+/* select_action for every env of st.  blocks_in NULL: the input is prep_state2 of each env's current
+ * state, computed in the kernel (the rows be_observe_blocks writes); else the caller's (N, 29) u8 rows.
+ * blocks_out, if given, receives the (N, 29) rows be_observe_blocks would write for st.
+ * out->action is required, out->log_prob and out->probs (N, A) are optional, out->value must be
+ * NULL (BE_E_INVALID).  One launch, asynchronous on stream, graph-capturable.                    */
+int be_mlp_act(be_mlp* mlp, const be_state* st, const uint8_t* blocks_in, uint8_t* blocks_out, const be_act_out* out,
+               uint64_t seed, void* stream);
+/* Bytes of the packed weight image (staged once per workgroup in LDS). */
+int64_t be_mlp_bytes(const be_mlp* mlp);
+
 /* ---- A2C targets: the batched finish_episode (examples/ball_cnn_ac3.py:222-246) ----
  * From a recorded rollout of `steps` rows of ctx's N envs -- contiguous (steps, N) device
  * arrays: rewards f64, dones u8 0/1 (what be_out.done and the rollouts write), values f32 or
