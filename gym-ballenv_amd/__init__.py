@@ -33,7 +33,8 @@ def __getattr__(name):
         from . import rollout
         return getattr(rollout, name)
     if name in ("BlockPolicy", "HipBlockPolicy", "BlockRollout", "torch_block_select_action", "reinforce_losses",
-                "reinforce_update", "reference_block_weights"):
+                "reinforce_update", "reference_block_weights", "BlockGrad", "supervised_losses",
+                "supervised_update", "reference_supervise_data"):
         from . import block_policy
         return getattr(block_policy, name)
     if name == "BatchedBoard":
@@ -49,4 +50,5 @@ __all__ = ["EnvConfig", "MOVE_LIST", "step_bytes", "survey_step_bytes", "Box", "
            "BallEnv", "make", "TimeLimit", "shard", "gather_stats", "combine_stats", "Policy", "HipPolicy",
            "torch_select_action", "Rollout", "a2c_losses", "a2c_update", "a2c_targets", "A2CTargets",
            "A2CGrad", "HipAdam", "A2CTrainer", "BatchedBoard", "BlockPolicy", "HipBlockPolicy", "BlockRollout",
-           "torch_block_select_action", "reinforce_losses", "reinforce_update", "reference_block_weights"]
+           "torch_block_select_action", "reinforce_losses", "reinforce_update", "reference_block_weights",
+           "BlockGrad", "supervised_losses", "supervised_update", "reference_supervise_data"]

@@ -29,6 +29,7 @@ EXPORTS = ("be_abi_version", "be_config_default", "be_config_check", "be_step_by
            "be_pool_fill", "be_pool_invalidate", "be_pool_set_period", "be_pool_period", "be_pool_bytes", "be_pool_entry", "be_policy_create", "be_policy_destroy", "be_policy_load", "be_policy_act",
            "be_policy_rollout", "be_policy_bytes", "be_observe_blocks",
            "be_mlp_create", "be_mlp_destroy", "be_mlp_load", "be_mlp_act", "be_mlp_bytes",
+           "be_mlp_grad_workspace_bytes", "be_mlp_grad",
            "be_board_config_default", "be_board_create", "be_board_destroy", "be_board_last_error",
            "be_board_reset", "be_board_step", "be_board_rollout", "be_board_observe", "be_board_status",
            "be_board_pool_bytes")
@@ -87,6 +88,20 @@ class BeA2CGrads(C.Structure):
     _fields_ = [("fc1_weight", C.c_void_p), ("fc1_bias", C.c_void_p), ("action_head_weight", C.c_void_p),
                 ("action_head_bias", C.c_void_p), ("value_head_weight", C.c_void_p), ("value_head_bias", C.c_void_p),
                 ("losses", C.c_void_p)]
+
+
+class BeMlpWeights(C.Structure):
+    _fields_ = [("w1", C.c_void_p), ("b1", C.c_void_p), ("w2", C.c_void_p), ("b2", C.c_void_p), ("w3", C.c_void_p),
+                ("b3", C.c_void_p), ("layers", C.c_int32), ("hidden1", C.c_int32), ("hidden2", C.c_int32),
+                ("num_actions", C.c_int32), ("final_relu", C.c_int32)]
+
+
+class BeMlpGrads(C.Structure):
+    _fields_ = [("w1", C.c_void_p), ("b1", C.c_void_p), ("w2", C.c_void_p), ("b2", C.c_void_p), ("w3", C.c_void_p),
+                ("b3", C.c_void_p), ("losses", C.c_void_p)]
+
+
+MLP_LOSS_REINFORCE, MLP_LOSS_XENT = 0, 1
 
 
 class BeA2CTensors(C.Structure):
@@ -175,6 +190,9 @@ def lib() -> C.CDLL:
         "be_mlp_load": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp]),
         "be_mlp_act": (C.c_int, [vp, P(BeState), vp, vp, P(BeActOut), u64, vp]),
         "be_mlp_bytes": (i64, [vp]),
+        "be_mlp_grad_workspace_bytes": (i64, [vp, i32, i32, i32, i32]),
+        "be_mlp_grad": (C.c_int, [vp, vp, vp, vp, vp, i64, i32, C.c_double, P(BeMlpWeights), vp, i64, P(BeMlpGrads),
+                                  vp]),
         "be_a2c_targets": (C.c_int, [vp, vp, vp, vp, vp, i32, C.c_double, C.c_double, P(BeA2COut), vp]),
         "be_a2c_grad_workspace_bytes": (i64, [vp, i32, i32]),
         "be_a2c_grad": (C.c_int, [vp, vp, vp, vp, vp, i64, P(BeA2CWeights), vp, i64, P(BeA2CGrads), vp]),

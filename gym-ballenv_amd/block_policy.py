@@ -15,7 +15,10 @@ kernel in csrc/mlp_policy.hip (``be_mlp_act``), which computes ``prep_state2`` o
 itself: the 29-byte row makes no round trip.  ``BlockRollout`` is the T-step loop of
 ``be_mlp_act`` + ``be_step`` writing straight into (T, N) buffers, capturable into HIP graphs;
 ``reinforce_losses`` / ``reinforce_update`` are the batched ``finish_episode`` over such a record
-(targets from ``be_a2c_targets``, gradients from torch autograd over the recorded rows).
+(targets from ``be_a2c_targets``; gradients from torch autograd over the recorded rows, or with
+grads="hip" from ``BlockGrad``: ``be_mlp_grad``, csrc/mlp_grad.hip, straight from the u8 rows).
+``supervised_losses`` / ``supervised_update`` are one minibatch of examples/train_supervise.py:66-101 on the
+same network (mean cross-entropy; ``reference_supervise_data`` is the reference's own training set).
 ``torch_block_select_action`` is the same computation in plain PyTorch fp32 -- the numerics
 reference of the tests.
 """
@@ -36,6 +39,10 @@ BLOCKS = 29                      # prep_state2's row: 4 quadrant + 5 x 5 blocks
 # be_mlp_act's work split (csrc/mlp_policy.hip): a persistent grid of one workgroup per compute unit,
 # WAVES waves each, a wave taking TILE envs per round (tile t of G workgroups: workgroup t % G, wave t // G % WAVES)
 TILE, WAVES = 16, 8
+# be_mlp_grad's (csrc/mlp_grad.hip): a persistent grid of one workgroup per compute unit (at most
+# GRAD_MAX_SLOTS), GRAD_WAVES waves each, a workgroup taking GRAD_TILE rows per round (tile t of G workgroups:
+# workgroup t % G, round t // G)
+GRAD_TILE, GRAD_WAVES, GRAD_MAX_SLOTS = 64, 4, 1024
 _KINDS = ("supervised3", "reinforce2")
 
 
@@ -308,14 +315,124 @@ def reinforce_losses(policy: BlockPolicy, blocks: torch.Tensor, actions: torch.T
     return -(logp.double() * Rn.double())[valid].sum()      # products and sum in f64: no rounding of its own
 
 
-def reinforce_update(rollout: BlockRollout, optimizer, gamma: float = 0.99, targets: str = "hip") -> float:
+class BlockGrad:
+    """``be_mlp_grad`` bound to one BatchedBallEnv and one BlockPolicy: the loss sum of ``reinforce_losses``
+    (loss="reinforce") or of ``supervised_losses`` (loss="xent", with scale = 1 / batch for its mean) and
+    what ``loss.backward()`` leaves in each ``.grad``, from the recorded u8 block counts in two
+    launches (include/ballenv.h pins the arithmetic; reproducible bit for bit).
+
+    Owns the workspace, the gradient tensors (``.grads``, keyed like ``policy.state_dict()``) and the
+    f64 pair ``.losses`` (scale * the sum of the row losses, the number of active rows); nothing is
+    allocated per call, so a call can be graph-captured.  The weights are read from the module's
+    parameters at call time (fp32, contiguous, on the env's device)."""
+
+    LOSSES = {"reinforce": _abi.MLP_LOSS_REINFORCE, "xent": _abi.MLP_LOSS_XENT}
+
+    def __init__(self, env, policy: BlockPolicy):
+        self.env, self.policy = env, policy
+        self._lib = _abi.lib()
+        dev = env.device
+        self.layers, self.hidden1, self.hidden2 = policy.layers, policy.hidden1, policy.hidden2
+        self.num_actions, self.final_relu = policy.num_actions, policy.final_relu
+        nbytes = int(self._lib.be_mlp_grad_workspace_bytes(env._ctx, self.layers, self.hidden1, self.hidden2,
+                                                           self.num_actions))
+        if nbytes < 0:
+            _abi.check(nbytes, env._ctx)
+        self.workspace = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+        self._names = [f"affine{i + 1}.{w}" for i in range(self.layers) for w in ("weight", "bias")]
+        sd = policy.state_dict()
+        self.grads = {k: torch.zeros(sd[k].shape, dtype=torch.float32, device=dev) for k in self._names}
+        self.losses = torch.zeros(2, dtype=torch.float64, device=dev)
+        ptrs = [self.grads[k].data_ptr() for k in self._names] + [None] * (6 - len(self._names))
+        self._g = _abi.BeMlpGrads(*ptrs, self.losses.data_ptr())
+        self._weights = None
+
+    def _params(self):
+        ps = dict(self.policy.named_parameters())
+        ws = []
+        for k in self._names:
+            w = ps[k].detach()
+            if w.dtype != torch.float32 or not w.is_contiguous() or w.device != self.env.device or \
+                    w.shape != self.grads[k].shape:
+                raise ValueError(f"policy parameter {k} must be a contiguous f32 tensor of the shape BlockGrad was "
+                                 "made for, on the env's device")
+            ws.append(w)
+        return ws
+
+    def __call__(self, blocks: torch.Tensor, actions: torch.Tensor, coef: Optional[torch.Tensor] = None,
+                 valid: Optional[torch.Tensor] = None, loss: str = "reinforce", scale: float = 1.0):
+        """blocks (T, N, 29) or (rows, 29) u8; actions u8 (the labels with loss="xent"), coef f32 or None
+        (= 1), valid u8 / bool or None (= every row), each (T, N) or (rows,): contiguous, on the env's
+        device.  Asynchronous on the caller's current stream.  Returns ``.grads``."""
+        dev = self.env.device
+        if loss not in self.LOSSES:
+            raise ValueError("loss must be 'reinforce' or 'xent'")
+        if blocks.dtype != torch.uint8 or blocks.dim() not in (2, 3) or blocks.shape[-1] != BLOCKS or \
+                not blocks.is_contiguous() or blocks.device != dev:
+            raise ValueError("blocks must be a (T, N, 29) or (rows, 29) contiguous u8 tensor on the env's device")
+        lead = tuple(blocks.shape[:-1])
+        if actions.dtype != torch.uint8 or tuple(actions.shape) != lead or not actions.is_contiguous() or \
+                actions.device != dev:
+            raise ValueError("actions must be a contiguous u8 tensor of blocks' leading shape on the env's device")
+        if coef is not None and (coef.dtype != torch.float32 or tuple(coef.shape) != lead or
+                                 not coef.is_contiguous() or coef.device != dev):
+            raise ValueError("coef must be a contiguous f32 tensor of blocks' leading shape on the env's device")
+        if valid is not None and (valid.dtype not in (torch.bool, torch.uint8) or tuple(valid.shape) != lead or
+                                  not valid.is_contiguous() or valid.device != dev):
+            raise ValueError("valid must be a contiguous bool / u8 tensor of blocks' leading shape on the env's device")
+        rows = 1
+        for n in lead:
+            rows *= int(n)
+        ws = self._params()
+        ptrs = [x.data_ptr() for x in ws] + [None] * (6 - len(ws))
+        w = _abi.BeMlpWeights(*ptrs, self.layers, self.hidden1, self.hidden2, self.num_actions, int(self.final_relu))
+        rc = self._lib.be_mlp_grad(self.env._ctx, blocks.data_ptr(), actions.data_ptr(),
+                                   None if coef is None else coef.data_ptr(),
+                                   None if valid is None else valid.data_ptr(), rows, self.LOSSES[loss], float(scale),
+                                   C.byref(w), self.workspace.data_ptr(), self.workspace.numel() * 8,
+                                   C.byref(self._g), self.env._stream())
+        if rc:
+            _abi.check(rc, self.env._ctx)
+        self._weights = ws          # keep alive until the kernels have run
+        return self.grads
+
+    def assign(self) -> None:
+        """The gradients of the last call into the module's ``.grad`` (copies; stream-ordered)."""
+        for k, prm in self.policy.named_parameters():
+            if prm.grad is None:
+                prm.grad = self.grads[k].clone()
+            else:
+                prm.grad.copy_(self.grads[k])
+
+
+def reinforce_update(rollout: BlockRollout, optimizer, gamma: float = 0.99, targets: str = "hip",
+                     grads: str = "torch") -> float:
     """One REINFORCE step on a recorded rollout (record_obs=True): the targets (targets="hip":
     ``be_a2c_targets`` with no values; "torch": ``reinforce_losses``' own), loss.backward(),
-    optimizer.step(), then the new weights re-packed for the HIP kernel.  Returns the loss value."""
+    optimizer.step(), then the new weights re-packed for the HIP kernel.  Returns the loss value.
+    grads: "torch" (``reinforce_losses`` + autograd) or "hip" (``BlockGrad``, cached on the rollout: the
+    loss and every .grad from ``be_mlp_grad``, no autograd graph and no f32 copy of the rows; needs
+    targets="hip")."""
     if rollout.blocks is None:
         raise ValueError("reinforce_update needs BlockRollout(record_obs=True)")
     if targets not in ("torch", "hip"):
         raise ValueError("targets must be 'torch' or 'hip'")
+    if grads not in ("torch", "hip"):
+        raise ValueError("grads must be 'torch' or 'hip'")
+    if grads == "hip":
+        if targets != "hip":
+            raise ValueError("grads='hip' needs targets='hip'")
+        from .rollout import a2c_targets
+        t = a2c_targets(rollout.env, rollout.rewards, rollout.dones, None, gamma, with_returns=False)
+        bg = getattr(rollout, "_block_grad", None)
+        if bg is None or bg.policy is not rollout.policy:
+            bg = rollout._block_grad = BlockGrad(rollout.env, rollout.policy)
+        bg(rollout.blocks, rollout.actions, t.returns_norm, t.valid, loss="reinforce", scale=1.0)
+        bg.assign()
+        loss = float(bg.losses[0])
+        optimizer.step()
+        rollout.hp.load(rollout.policy)
+        return loss
     tg = None
     if targets == "hip":
         from .rollout import a2c_targets
@@ -327,4 +444,46 @@ def reinforce_update(rollout: BlockRollout, optimizer, gamma: float = 0.99, targ
     loss.backward()
     optimizer.step()
     rollout.hp.load(rollout.policy)
+    return float(loss.detach())
+
+
+def reference_supervise_data() -> Optional[str]:
+    """Path of the committed fixture of the reference's supervised training data (one recorded trial:
+    ``blocks`` (3186, 29) u8, ``labels`` (3186,) u8; tests/golden/make_supervise_fixture.py), if present."""
+    p = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(__file__))), "tests", "golden",
+                     "supervise_trial2.npz")
+    return p if os.path.exists(p) else None
+
+
+def supervised_losses(policy: BlockPolicy, blocks: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+    """The loss of examples/train_supervise.py:74, :90-97 for one minibatch: mean ``CrossEntropyLoss`` of the
+    logits on blocks (B, 29) against labels (B,), in the module's own precision (plain torch: the
+    numerics reference of ``be_mlp_grad``'s cross-entropy mode)."""
+    x = blocks.to(policy.affine1.weight.dtype)
+    return F.cross_entropy(policy.logits(x), labels.long())
+
+
+def supervised_update(policy: BlockPolicy, blocks: torch.Tensor, labels: torch.Tensor, optimizer, grads: str = "torch",
+                      grad: Optional[BlockGrad] = None) -> float:
+    """One minibatch step of examples/train_supervise.py:90-101: the mean cross-entropy, its gradients,
+    optimizer.step().  Returns the loss value.  grads: "torch" (``supervised_losses`` + autograd) or "hip"
+    (``grad``, a ``BlockGrad`` made for ``policy``: ``be_mlp_grad`` with scale = 1 / batch; blocks u8
+    and labels u8 or integer, on its env's device).  The caller re-packs a ``HipBlockPolicy`` (``load``)
+    when it next acts with the new weights."""
+    if grads not in ("torch", "hip"):
+        raise ValueError("grads must be 'torch' or 'hip'")
+    if grads == "hip":
+        if grad is None or grad.policy is not policy:
+            raise ValueError("grads='hip' needs grad=BlockGrad(env, policy)")
+        if labels.dtype != torch.uint8:
+            labels = labels.to(torch.uint8)
+        grad(blocks, labels.contiguous(), None, None, loss="xent", scale=1.0 / max(1, int(blocks.shape[0])))
+        grad.assign()
+        loss = float(grad.losses[0])
+        optimizer.step()
+        return loss
+    loss = supervised_losses(policy, blocks, labels)
+    optimizer.zero_grad()
+    loss.backward()
+    optimizer.step()
     return float(loss.detach())

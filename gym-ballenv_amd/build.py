@@ -23,6 +23,9 @@ object) and linked into one shared library:
                     operations with -ffp-contract=off, as every unit: the pinned arithmetic has no FMA)
   csrc/mlp_policy.hip select_action of the REINFORCE / supervised block-count MLP (f32 MFMAs) straight
                     from the env state; shares blocks_core.h (prep_state2 of one env) with features.hip
+  csrc/mlp_grad.hip the block-count MLP's REINFORCE / cross-entropy losses and gradients of recorded rows
+                    (f32 MFMAs; no VGPR_MFMA, for a2c_grad.hip's reason: the gradient accumulators live
+                    for the whole kernel, the AGPR half of the register file is where they belong)
 """
 from __future__ import annotations
 
@@ -49,7 +52,7 @@ VGPR_MFMA = ["-mllvm", "-amdgpu-mfma-vgpr-form"]
 KARG_PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
 UNITS = {"ballenv.hip": [*VGPR_MFMA, *KARG_PRELOAD], "abi.hip": [], "policy.hip": ["-fno-slp-vectorize", *VGPR_MFMA],
          "features.hip": [], "board.hip": [], "a2c.hip": [], "a2c_grad.hip": [], "a2c_adam.hip": [],
-         "mlp_policy.hip": []}
+         "mlp_policy.hip": [], "mlp_grad.hip": []}
 HEADERS = [HDR, *(os.path.join(CSRC, h) for h in ("philox.h", "internal.h", "host_logic.h", "pool_layout.h", "policy_core.h", "blocks_core.h", "diag.h",
                                               "step_types.h"))]
 

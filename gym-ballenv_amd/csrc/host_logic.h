@@ -107,4 +107,39 @@ inline be_out be_out_at(const be_out& out, int64_t s, int64_t N, int64_t F) {
   return o;
 }
 
+// be_mlp_grad's argument checks that need no device (mlp_grad.hip): the block MLP's shape against
+// be_mlp_create's bounds and w3 / b3 against the layer count.  NULL: fine, else the message.
+inline const char* mlp_grad_shape_error(int layers, int hidden1, int hidden2, int num_actions) {
+  if (layers != 2 && layers != 3) return "be_mlp_grad: layers must be 2 or 3";
+  if (hidden1 < 1 || hidden1 > 128) return "be_mlp_grad: hidden1 must be in [1, 128]";
+  if (layers == 3 && (hidden2 < 1 || hidden2 > 128)) return "be_mlp_grad: hidden2 must be in [1, 128]";
+  if (layers == 2 && hidden2 != 0) return "be_mlp_grad: hidden2 must be 0 with 2 layers";
+  if (num_actions < 1 || num_actions > 15) return "be_mlp_grad: num_actions must be in [1, 15]";
+  return nullptr;
+}
+inline const char* mlp_grad_last_layer_error(int layers, const void* w3, const void* b3) {
+  if (layers == 3 && (!w3 || !b3)) return "be_mlp_grad: 3 layers need w3 and b3 (weights and grads)";
+  if (layers == 2 && (w3 || b3)) return "be_mlp_grad: w3 and b3 must be NULL with 2 layers (weights and grads)";
+  return nullptr;
+}
+// One workgroup's slot of be_mlp_grad's workspace (offsets in floats; the gradient elements in
+// state_dict order, then two f64: the sum of the row losses and the number of active rows).
+struct MlpGradSlot {
+  int32_t o_b1, o_w2, o_b2, o_w3, o_b3, P;      // gW1 at 0; P gradient elements
+  int32_t loss_off, slot_bytes;                 // bytes
+};
+inline MlpGradSlot mlp_grad_slot(int layers, int H1, int H2, int A) {
+  MlpGradSlot s{};
+  const int n2 = layers == 3 ? H2 : A;          // rows of affine2
+  s.o_b1 = H1 * 29;
+  s.o_w2 = s.o_b1 + H1;
+  s.o_b2 = s.o_w2 + n2 * H1;
+  s.o_w3 = s.o_b2 + n2;
+  s.o_b3 = s.o_w3 + (layers == 3 ? A * H2 : 0);
+  s.P = s.o_b3 + (layers == 3 ? A : 0);
+  s.loss_off = (s.P * 4 + 7) / 8 * 8;
+  s.slot_bytes = s.loss_off + 2 * 8;
+  return s;
+}
+
 }  // namespace behost

@@ -360,6 +360,57 @@ int be_mlp_act(be_mlp* mlp, const be_state* st, const uint8_t* blocks_in, uint8_
 /* Bytes of the packed weight image (staged once per workgroup in LDS). */
 int64_t be_mlp_bytes(const be_mlp* mlp);
 
+/* ---- the block-count MLP's losses and gradients: both of the reference's training loops ----
+ *   finish_episode       examples/ball_env_reinforce.py:88-108  sum of -Categorical(probs).log_prob(a) * R^
+ *   the supervised loop  examples/train_supervise.py:66-101     mean CrossEntropyLoss on the logits
+ * The loss of the network above over `rows` recorded rows (every row offset is 64-bit) and its
+ * gradients, i.e. what loss.backward() leaves in each .grad.  Contiguous device arrays: blocks
+ * (rows, 29) u8, actions (rows) u8 (the labels with BE_MLP_LOSS_XENT), coef (rows) f32 or NULL (= 1),
+ * valid (rows) u8 or NULL (= every row).  A row is active when it is valid and action < num_actions;
+ * any other row adds exactly +0.  Per active row, in f32 (a = its action, c = its coef,
+ * eps = FLT_EPSILON):
+ *   x = the 29 counts as f32;  pre1 = W1 x + b1;  h1 = max(pre1, 0)
+ *   3 layers: pre2 = W2 h1 + b2;  h2 = max(pre2, 0)
+ *   zp = W_last h + b_last;  z = final_relu ? max(zp, 0) : zp
+ *   m = max z;  e_j = exp(z_j - m);  S = sum e_j;  p_j = e_j / S
+ *   BE_MLP_LOSS_REINFORCE (Categorical(probs).log_prob: the probabilities clamped to [eps, 1 - eps]):
+ *     loss += -c * log(min(max(p_a, eps), 1 - eps))
+ *     dz_j = c * (p_j - [j == a]) if eps <= p_a <= 1 - eps, else 0   (the clamp passes no gradient outside
+ *     its bounds; Categorical's p / sum p has no gradient of its own and is left out)
+ *   BE_MLP_LOSS_XENT (CrossEntropyLoss on z):
+ *     loss += -c * (z_a - m - log S);   dz_j = c * (p_j - [j == a])
+ *   dzp_j = (final_relu && zp_j <= 0) ? 0 : dz_j
+ *   gW_last += dzp (x) h;  gb_last += dzp;  dh = W_last^T dzp;  dpre = pre > 0 ? dh : 0   (each hidden layer)
+ *   3 layers: gW2 += dpre2 (x) h1;  gb2 += dpre2;  dh1 = W2^T dpre2
+ *   gW1 += dpre1 (x) x;  gb1 += dpre1
+ * Every product is an f32 fma chain on v_mfma_f32_16x16x4_f32 (csrc/mlp_grad.hip has the operand order).
+ * No float atomics: each workgroup of a grid that depends only on rows and the device adds its
+ * rows in a fixed order and writes its sums to `workspace`; a second kernel adds the workgroups'
+ * sums in workgroup order in f64, multiplies by `scale` in f64 and rounds once to f32.  losses[0] is
+ * scale * the f64 sum of the row losses, losses[1] the number of active rows.  scale: 1 / batch for the
+ * supervised mean; 1 for REINFORCE with coef = returns_norm.  Two calls on the same inputs and
+ * device give the same bits whatever the workspace held.  Every output element is written on every
+ * call (zeros when no row is active; rows = 0 is valid).  Asynchronous on `stream`, no allocation
+ * and no synchronisation (graph-capturable).  BE_E_INVALID, with nothing launched: a NULL ctx or
+ * required pointer, a shape outside be_mlp_create's bounds, w3 / b3 not matching layers, an unknown
+ * loss, a workspace that is too small.                                                        */
+typedef struct be_mlp_weights {     /* state_dict layout, as be_mlp_load takes them, and the shape */
+  const float *w1, *b1, *w2, *b2, *w3, *b3;          /* 2 layers: w3 = b3 = NULL                     */
+  int32_t layers, hidden1, hidden2, num_actions, final_relu;   /* be_mlp_create's bounds            */
+} be_mlp_weights;
+typedef struct be_mlp_grads {       /* the same shapes: what loss.backward() leaves in each .grad  */
+  float *w1, *b1, *w2, *b2, *w3, *b3;                /* 2 layers: w3 = b3 = NULL                     */
+  double* losses;                   /* [2]: scale * sum of row losses, number of active rows       */
+} be_mlp_grads;
+#define BE_MLP_LOSS_REINFORCE 0
+#define BE_MLP_LOSS_XENT      1
+/* Bytes of workspace be_mlp_grad needs on ctx's device (8-byte aligned; independent of rows);
+ * < 0: an error code.                                                                       */
+int64_t be_mlp_grad_workspace_bytes(be_ctx* ctx, int32_t layers, int32_t hidden1, int32_t hidden2, int32_t num_actions);
+int be_mlp_grad(be_ctx* ctx, const uint8_t* blocks, const uint8_t* actions, const float* coef, const uint8_t* valid,
+                int64_t rows, int32_t loss, double scale, const be_mlp_weights* weights,
+                void* workspace, int64_t workspace_bytes, const be_mlp_grads* grads, void* stream);
+
 /* ---- A2C targets: the batched finish_episode (examples/ball_cnn_ac3.py:222-246) ----
  * From a recorded rollout of `steps` rows of ctx's N envs -- contiguous (steps, N) device
  * arrays: rewards f64, dones u8 0/1 (what be_out.done and the rollouts write), values f32 or
