@@ -34,7 +34,8 @@ def __getattr__(name):
         return getattr(rollout, name)
     if name in ("BlockPolicy", "HipBlockPolicy", "BlockRollout", "torch_block_select_action", "reinforce_losses",
                 "reinforce_update", "reference_block_weights", "BlockGrad", "supervised_losses",
-                "supervised_update", "reference_supervise_data"):
+                "supervised_update", "reference_supervise_data", "HipBlockOptim", "BlockTrainer",
+                "SupervisedTrainer"):
         from . import block_policy
         return getattr(block_policy, name)
     if name == "BatchedBoard":
@@ -51,4 +52,5 @@ __all__ = ["EnvConfig", "MOVE_LIST", "step_bytes", "survey_step_bytes", "Box", "
            "torch_select_action", "Rollout", "a2c_losses", "a2c_update", "a2c_targets", "A2CTargets",
            "A2CGrad", "HipAdam", "A2CTrainer", "BatchedBoard", "BlockPolicy", "HipBlockPolicy", "BlockRollout",
            "torch_block_select_action", "reinforce_losses", "reinforce_update", "reference_block_weights",
-           "BlockGrad", "supervised_losses", "supervised_update", "reference_supervise_data"]
+           "BlockGrad", "supervised_losses", "supervised_update", "reference_supervise_data", "HipBlockOptim",
+           "BlockTrainer", "SupervisedTrainer"]

@@ -29,7 +29,7 @@ EXPORTS = ("be_abi_version", "be_config_default", "be_config_check", "be_step_by
            "be_pool_fill", "be_pool_invalidate", "be_pool_set_period", "be_pool_period", "be_pool_bytes", "be_pool_entry", "be_policy_create", "be_policy_destroy", "be_policy_load", "be_policy_act",
            "be_policy_rollout", "be_policy_bytes", "be_observe_blocks",
            "be_mlp_create", "be_mlp_destroy", "be_mlp_load", "be_mlp_act", "be_mlp_bytes",
-           "be_mlp_grad_workspace_bytes", "be_mlp_grad",
+           "be_mlp_grad_workspace_bytes", "be_mlp_grad", "be_mlp_opt",
            "be_board_config_default", "be_board_create", "be_board_destroy", "be_board_last_error",
            "be_board_reset", "be_board_step", "be_board_rollout", "be_board_observe", "be_board_status",
            "be_board_pool_bytes")
@@ -102,6 +102,14 @@ class BeMlpGrads(C.Structure):
 
 
 MLP_LOSS_REINFORCE, MLP_LOSS_XENT = 0, 1
+
+
+class BeMlpTensors(C.Structure):
+    _fields_ = [("w1", C.c_void_p), ("b1", C.c_void_p), ("w2", C.c_void_p), ("b2", C.c_void_p), ("w3", C.c_void_p),
+                ("b3", C.c_void_p)]
+
+
+MLP_OPT_ADAM, MLP_OPT_SGD = 0, 1
 
 
 class BeA2CTensors(C.Structure):
@@ -193,6 +201,8 @@ def lib() -> C.CDLL:
         "be_mlp_grad_workspace_bytes": (i64, [vp, i32, i32, i32, i32]),
         "be_mlp_grad": (C.c_int, [vp, vp, vp, vp, vp, i64, i32, C.c_double, P(BeMlpWeights), vp, i64, P(BeMlpGrads),
                                   vp]),
+        "be_mlp_opt": (C.c_int, [vp, i32, P(BeMlpTensors), P(BeMlpTensors), P(BeMlpTensors), P(BeMlpTensors), vp,
+                                 C.c_double, C.c_double, C.c_double, vp, vp, i32, vp]),
         "be_a2c_targets": (C.c_int, [vp, vp, vp, vp, vp, i32, C.c_double, C.c_double, P(BeA2COut), vp]),
         "be_a2c_grad_workspace_bytes": (i64, [vp, i32, i32]),
         "be_a2c_grad": (C.c_int, [vp, vp, vp, vp, vp, i64, P(BeA2CWeights), vp, i64, P(BeA2CGrads), vp]),

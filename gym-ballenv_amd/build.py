@@ -22,7 +22,8 @@ object) and linked into one shared library:
   csrc/a2c_adam.hip the Adam step on the six Policy tensors and the re-pack of the policy image (f64
                     operations with -ffp-contract=off, as every unit: the pinned arithmetic has no FMA)
   csrc/mlp_policy.hip select_action of the REINFORCE / supervised block-count MLP (f32 MFMAs) straight
-                    from the env state; shares blocks_core.h (prep_state2 of one env) with features.hip
+                    from the env state; shares blocks_core.h (prep_state2 of one env) with features.hip;
+                    and next to its pack kernel the Adam / SGD step fused with the re-pack (be_mlp_opt)
   csrc/mlp_grad.hip the block-count MLP's REINFORCE / cross-entropy losses and gradients of recorded rows
                     (f32 MFMAs; no VGPR_MFMA, for a2c_grad.hip's reason: the gradient accumulators live
                     for the whole kernel, the AGPR half of the register file is where they belong)

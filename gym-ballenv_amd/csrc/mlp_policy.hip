@@ -12,6 +12,9 @@
 //   be_mlp_load   one launch: the f32 state_dict arrays into the padded image the kernel stages
 //   be_mlp_act    one launch: [prep_state2 ->] forward -> softmax -> draw, the arithmetic
 //                 include/ballenv.h pins
+//   be_mlp_opt    two launches: optimizer.step() of both training loops (Adam, ball_env_reinforce.py:196;
+//                 SGD, train_supervise.py:75) on the state_dict tensors in place, fused with be_mlp_load's
+//                 pack of the new weights; then the one-thread state kernel
 //
 // Every product runs on v_mfma_f32_16x16x4_f32 (an exact f32 fma chain) as D = W . x^T: the
 // weights are the A operand (row = output unit), a tile of 16 envs the B operand (column = env),
@@ -125,6 +128,133 @@ __global__ __launch_bounds__(256) void mlp_pack_kernel(MPack a, float* img, MlpL
     }
     img[i] = v;
   }
+}
+
+// be_mlp_opt: the optimiser step on the four or six tensors and the pack above, inverted.  Thread i
+// takes source element i of w1 | b1 | w2 | b2 | wl | bl laid end to end (w2 / b2: the second hidden
+// layer, empty with 2 layers; wl / bl: the last layer), so a wave reads w, g, m, v and writes w, m, v
+// as consecutive floats, and scatters its new weight to the one image index that mlp_pack_kernel fills
+// from that element:
+//   f1       (m, k) -> kk = k >> 2, ht = m >> 4, lane = (k & 3) << 4 | (m & 15)
+//   f2 / f3  (m, k) -> s = (k >> 4) << 2 | (k & 3), l4 = (k >> 2) & 3, mt = m >> 4, lane = l4 << 4 | (m & 15)
+// The map is a bijection onto the image's non-pad part: no element has two writers and no thread reads
+// what another writes.  Pad entries are zero since be_mlp_create (every be_mlp_load rewrites them as
+// zeros, and the shape never changes); the last 16 threads write hb, which completes an image that was
+// never loaded.
+struct MSix { float *w1, *b1, *w2, *b2, *wl, *bl; };
+
+struct OParams {
+  MSix w, g, m, v;           // params, grads (read only), exp_avg, exp_avg_sq (Adam only)
+  const double* state;       // [t, beta1^t, beta2^t, lr] before the call
+  double beta1, beta2, eps;
+  float* img;
+  MlpLayout L;
+  int32_t H1, H2, A;
+  int32_t e0, e1, e2, e3, e4, e5;      // the running ends of the six tensors in the element order
+};
+
+struct OStep { double beta1, beta2, omb1, omb2, eps, bc2s, ss; };
+
+template <int KIND>
+__global__ __launch_bounds__(256) void mlp_opt_kernel(OParams p) {
+  const MlpLayout& L = p.L;
+  const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+  if (i >= p.e5 + MLP_NO) return;
+  if (i >= p.e5) {
+    const int m = i - p.e5;
+    p.img[L.hb + m] = (m < p.A || m == MLP_NO - 1) ? 0.0f : -INFINITY;
+    return;
+  }
+  const int HL = L.layers == 3 ? p.H2 : p.H1;
+  float *w, *m1p, *m2p;
+  const float* g;
+  int j, dst;
+  if (i < p.e0) {
+    j = i;
+    const int m = j / BLK_ROW, k = j - m * BLK_ROW;
+    dst = L.f1 + (((k >> 2) * L.HT1 + (m >> 4)) << 6) + (((k & 3) << 4) | (m & 15));
+    w = p.w.w1; g = p.g.w1; m1p = p.m.w1; m2p = p.v.w1;
+  } else if (i < p.e1) {
+    j = i - p.e0;
+    dst = L.b1 + j;
+    w = p.w.b1; g = p.g.b1; m1p = p.m.b1; m2p = p.v.b1;
+  } else if (i < p.e2) {
+    j = i - p.e1;
+    const int m = j / p.H1, k = j - m * p.H1, s = ((k >> 4) << 2) | (k & 3);
+    dst = L.f2 + ((s * L.HT2 + (m >> 4)) << 6) + ((((k >> 2) & 3) << 4) | (m & 15));
+    w = p.w.w2; g = p.g.w2; m1p = p.m.w2; m2p = p.v.w2;
+  } else if (i < p.e3) {
+    j = i - p.e2;
+    dst = L.b2 + j;
+    w = p.w.b2; g = p.g.b2; m1p = p.m.b2; m2p = p.v.b2;
+  } else if (i < p.e4) {
+    j = i - p.e3;
+    const int m = j / HL, k = j - m * HL, s = ((k >> 4) << 2) | (k & 3);
+    dst = L.f3 + (s << 6) + ((((k >> 2) & 3) << 4) | m);
+    w = p.w.wl; g = p.g.wl; m1p = p.m.wl; m2p = p.v.wl;
+  } else {
+    j = i - p.e4;
+    dst = L.b3 + j;
+    w = p.w.bl; g = p.g.bl; m1p = p.m.bl; m2p = p.v.bl;
+  }
+  // the pinned arithmetic of include/ballenv.h (no FMA: the unit is built with -ffp-contract=off)
+  const double gd = (double)g[j];
+  float wn;
+  if constexpr (KIND == BE_MLP_OPT_ADAM) {
+    const double p1 = p.state[1] * p.beta1, p2 = p.state[2] * p.beta2, lr = p.state[3];
+    const OStep c{p.beta1, p.beta2, 1.0 - p.beta1, 1.0 - p.beta2, p.eps, sqrt(1.0 - p2), lr / (1.0 - p1)};
+    const float m1 = (float)(c.beta1 * (double)m1p[j] + c.omb1 * gd);
+    const float v1 = (float)(c.beta2 * (double)m2p[j] + (c.omb2 * gd) * gd);
+    wn = (float)((double)w[j] - c.ss * ((double)m1 / (sqrt((double)v1) / c.bc2s + c.eps)));
+    m1p[j] = m1; m2p[j] = v1;
+  } else {
+    wn = (float)((double)w[j] - p.state[3] * gd);
+  }
+  w[j] = wn;
+  p.img[dst] = wn;
+}
+
+// One thread, behind the update kernel on the stream: the losses into row (t mod rows) of the log, then
+// the state's advance (SGD: the step count alone).
+__global__ void mlp_opt_advance(double* state, int32_t kind, double beta1, double beta2, const double* losses,
+                                double* loss_log, int32_t log_rows) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const double t = state[0];
+  if (loss_log) {
+    double* row = loss_log + 2 * ((int64_t)t % log_rows);
+    row[0] = losses[0]; row[1] = losses[1];
+  }
+  state[0] = t + 1.0;
+  if (kind == BE_MLP_OPT_ADAM) {
+    state[1] = state[1] * beta1;
+    state[2] = state[2] * beta2;
+  }
+}
+
+// the first pointer of a tensor set that is NULL or misaligned where the layer count needs it, or set
+// where it does not (w3 / b3 with 2 layers), as "<set>-><field>", or nullptr
+const char* mlp_bad_field(const be_mlp_tensors* t, int layers, const char* const (&names)[6]) {
+  const float* const ptrs[6] = {t->w1, t->b1, t->w2, t->b2, t->w3, t->b3};
+  for (int i = 0; i < 6; ++i) {
+    if (i >= 4 && layers == 2) {
+      if (ptrs[i]) return names[i];
+    } else if (!ptrs[i] || ((uintptr_t)ptrs[i] & 3)) {
+      return names[i];
+    }
+  }
+  return nullptr;
+}
+#define BE_MLP_NAMES(set) {set "->w1", set "->b1", set "->w2", set "->b2", set "->w3", set "->b3"}
+const char* const MN_PARAMS[6] = BE_MLP_NAMES("params");
+const char* const MN_GRADS[6] = BE_MLP_NAMES("grads");
+const char* const MN_AVG[6] = BE_MLP_NAMES("exp_avg");
+const char* const MN_SQ[6] = BE_MLP_NAMES("exp_avg_sq");
+
+// a tensor set in the kernel's order: with 2 layers the caller's w2 / b2 are the last layer
+MSix mlp_six(const be_mlp_tensors* t, int layers) {
+  if (!t) return MSix{};
+  return layers == 3 ? MSix{t->w1, t->b1, t->w2, t->b2, t->w3, t->b3}
+                     : MSix{t->w1, t->b1, nullptr, nullptr, t->w2, t->b2};
 }
 
 struct MParams {
@@ -373,6 +503,66 @@ int be_mlp_load(be_mlp* m, const float* w1, const float* b1, const float* w2, co
   hipLaunchKernelGGL(mlp_pack_kernel, dim3((unsigned)((m->L.total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a,
                      m->img, m->L);
   if (int rc = be_launched(be_ctx_err(ctx))) return rc;
+  m->loaded = true;
+  return BE_OK;
+}
+
+int be_mlp_opt(be_mlp* m, int32_t kind, const be_mlp_tensors* params, const be_mlp_tensors* grads,
+               const be_mlp_tensors* exp_avg, const be_mlp_tensors* exp_avg_sq, double* state, double beta1,
+               double beta2, double eps, const double* losses, double* loss_log, int32_t log_rows, void* stream) {
+  if (!m) return be_ctx_fail(nullptr, BE_E_INVALID, "be_mlp_opt: mlp is NULL");
+  be_ctx* ctx = m->ctx;
+  char* err = be_ctx_err(ctx);
+  const bool adam = kind == BE_MLP_OPT_ADAM;
+  if (!adam && kind != BE_MLP_OPT_SGD)
+    return be_ctx_fail(ctx, BE_E_INVALID, "be_mlp_opt: kind must be BE_MLP_OPT_ADAM or BE_MLP_OPT_SGD");
+  if (!params) return be_ctx_fail(ctx, BE_E_INVALID, "be_mlp_opt: params is NULL");
+  if (!grads) return be_ctx_fail(ctx, BE_E_INVALID, "be_mlp_opt: grads is NULL");
+  if (adam && !exp_avg) return be_ctx_fail(ctx, BE_E_INVALID, "be_mlp_opt: exp_avg is NULL (BE_MLP_OPT_ADAM needs it)");
+  if (adam && !exp_avg_sq)
+    return be_ctx_fail(ctx, BE_E_INVALID, "be_mlp_opt: exp_avg_sq is NULL (BE_MLP_OPT_ADAM needs it)");
+  if (!adam && (exp_avg || exp_avg_sq))
+    return be_ctx_fail(ctx, BE_E_INVALID, "be_mlp_opt: exp_avg and exp_avg_sq must be NULL with BE_MLP_OPT_SGD");
+  const struct { const be_mlp_tensors* t; const char* const (&names)[6]; } sets[4] = {
+      {params, MN_PARAMS}, {grads, MN_GRADS}, {exp_avg, MN_AVG}, {exp_avg_sq, MN_SQ}};
+  for (const auto& s : sets) {
+    if (!s.t) continue;
+    if (const char* name = mlp_bad_field(s.t, m->layers, s.names))
+      return be_fail(err, BE_E_INVALID,
+                     "be_mlp_opt: %s is NULL or not 4-byte aligned (w3 and b3: set with 3 layers, NULL with 2)", name);
+  }
+  if (!state || ((uintptr_t)state & 7))
+    return be_ctx_fail(ctx, BE_E_INVALID, "be_mlp_opt: state is NULL or not 8-byte aligned");
+  if (adam) {
+    if (!(beta1 >= 0.0 && beta1 < 1.0)) return be_ctx_fail(ctx, BE_E_INVALID, "be_mlp_opt: beta1 must be in [0, 1)");
+    if (!(beta2 >= 0.0 && beta2 < 1.0)) return be_ctx_fail(ctx, BE_E_INVALID, "be_mlp_opt: beta2 must be in [0, 1)");
+    if (!(eps >= 0.0)) return be_ctx_fail(ctx, BE_E_INVALID, "be_mlp_opt: eps must be >= 0");
+  }
+  if ((losses != nullptr) != (loss_log != nullptr))
+    return be_ctx_fail(ctx, BE_E_INVALID, "be_mlp_opt: losses and loss_log go together (both or neither)");
+  if (((uintptr_t)losses & 7) || ((uintptr_t)loss_log & 7))
+    return be_ctx_fail(ctx, BE_E_INVALID, "be_mlp_opt: losses / loss_log is not 8-byte aligned");
+  if (loss_log && log_rows < 1) return be_ctx_fail(ctx, BE_E_INVALID, "be_mlp_opt: log_rows must be >= 1");
+  BE_ENTER_DEVICE(err, m->cv.device);
+  OParams p{};
+  p.w = mlp_six(params, m->layers); p.g = mlp_six(grads, m->layers);
+  p.m = mlp_six(exp_avg, m->layers); p.v = mlp_six(exp_avg_sq, m->layers);
+  p.state = state; p.beta1 = beta1; p.beta2 = beta2; p.eps = eps;
+  p.img = m->img; p.L = m->L; p.H1 = m->H1; p.H2 = m->H2; p.A = m->A;
+  const int HL = m->layers == 3 ? m->H2 : m->H1;
+  p.e0 = m->H1 * BLK_ROW;
+  p.e1 = p.e0 + m->H1;
+  p.e2 = p.e1 + (m->layers == 3 ? m->H2 * m->H1 : 0);
+  p.e3 = p.e2 + (m->layers == 3 ? m->H2 : 0);
+  p.e4 = p.e3 + m->A * HL;
+  p.e5 = p.e4 + m->A;
+  const dim3 grid((unsigned)((p.e5 + MLP_NO + 255) / 256)), block(256);
+  hipStream_t hs = (hipStream_t)stream;
+  if (adam) hipLaunchKernelGGL((mlp_opt_kernel<BE_MLP_OPT_ADAM>), grid, block, 0, hs, p);
+  else hipLaunchKernelGGL((mlp_opt_kernel<BE_MLP_OPT_SGD>), grid, block, 0, hs, p);
+  if (int rc = be_launched(err)) return rc;
+  hipLaunchKernelGGL(mlp_opt_advance, dim3(1), dim3(64), 0, hs, state, kind, beta1, beta2, losses, loss_log, log_rows);
+  if (int rc = be_launched(err)) return rc;
   m->loaded = true;
   return BE_OK;
 }

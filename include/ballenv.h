@@ -411,6 +411,53 @@ int be_mlp_grad(be_ctx* ctx, const uint8_t* blocks, const uint8_t* actions, cons
                 int64_t rows, int32_t loss, double scale, const be_mlp_weights* weights,
                 void* workspace, int64_t workspace_bytes, const be_mlp_grads* grads, void* stream);
 
+/* ---- the block-count MLP's optimiser step and re-pack: optimizer.step() of both training loops ----
+ *   REINFORCE            examples/ball_env_reinforce.py:196, :105  optim.Adam(lr=1e-2)
+ *   the supervised loop  examples/train_supervise.py:75, :101      torch.optim.SGD(lr=1e-2)
+ * One optimiser step on the network's four (2 layers) or six tensors in place, and `mlp`'s packed
+ * image rebuilt from the new weights: afterwards the image holds exactly the bytes be_mlp_load would
+ * build from them, so be_mlp_act runs the updated network, and mlp counts as loaded.  mlp's layers,
+ * hidden1, hidden2 and num_actions define every shape (be_mlp_load's); an mlp that was never loaded is
+ * accepted (the step defines the whole image).
+ * All tensors are contiguous f32 device arrays in state_dict layout: params (updated), grads (read:
+ * what be_mlp_grad writes), and for BE_MLP_OPT_ADAM exp_avg and exp_avg_sq (updated; zeros for a
+ * fresh optimiser); BE_MLP_OPT_SGD takes exp_avg = exp_avg_sq = NULL.
+ * state: 4 f64 on the device, [t, beta1^t, beta2^t, lr], as be_a2c_adam's; a fresh optimiser holds
+ * [0, 1, 1, lr].  The learning rate lives on the device so that a captured graph follows a change of it.
+ * The arithmetic is pinned; every operation is one f64 operation, no FMA:
+ *   BE_MLP_OPT_ADAM (torch.optim.Adam with weight_decay = 0, amsgrad = False, maximize = False), the
+ *   arithmetic of be_a2c_adam:
+ *     t' = t + 1;  p1' = p1 * beta1;  p2' = p2 * beta2       (state after the call: [t', p1', p2', lr])
+ *     bc1 = 1 - p1';  bc2s = sqrt(1 - p2');  ss = lr / bc1
+ *     per element:  g = (double)grad
+ *       m' = (float)(beta1 * (double)m + (1 - beta1) * g)
+ *       v' = (float)(beta2 * (double)v + ((1 - beta2) * g) * g)
+ *       w' = (float)((double)w - ss * ((double)m' / (sqrt((double)v') / bc2s + eps)))
+ *   BE_MLP_OPT_SGD (torch.optim.SGD with momentum = 0, weight_decay = 0, nesterov = False):
+ *     per element:  w' = (float)((double)w - lr * (double)grad)
+ *     the state after the call: [t + 1, p1, p2, lr]; beta1, beta2 and eps are ignored
+ * Every element is computed from the state as it was before the call; the state advances exactly
+ * once per call, after all of them (a one-thread kernel behind the update kernel on `stream`).
+ * losses / loss_log: both NULL, or losses = the 2 f64 of be_mlp_grads.losses and loss_log a
+ * (log_rows, 2) f64 device array, log_rows >= 1: row (t mod log_rows) receives a copy of losses, t
+ * being the state's step count before the call -- a replayed graph logs every iteration's losses.
+ * Asynchronous on `stream`, no allocation and no synchronisation (graph-capturable as a linear
+ * chain); two launches: the update + pack kernel, the state kernel.
+ * BE_E_INVALID, with nothing launched: a NULL mlp; an unknown kind; a NULL params or grads; a NULL
+ * or not 4-byte aligned tensor of a given set, named in the message ("grads->w2"); w3 / b3 not
+ * matching the layer count; moment sets missing for ADAM or given to SGD; state NULL or not 8-byte
+ * aligned; for ADAM a beta outside [0, 1) or eps < 0; losses and loss_log not both or neither, or not
+ * 8-byte aligned; log_rows < 1 with a log.                                                        */
+typedef struct be_mlp_tensors {     /* f32 device arrays, state_dict layout, be_mlp_load's shapes  */
+  float *w1, *b1, *w2, *b2, *w3, *b3;                /* 2 layers: w3 = b3 = NULL                     */
+} be_mlp_tensors;
+#define BE_MLP_OPT_ADAM 0
+#define BE_MLP_OPT_SGD  1
+int be_mlp_opt(be_mlp* mlp, int32_t kind, const be_mlp_tensors* params, const be_mlp_tensors* grads,
+               const be_mlp_tensors* exp_avg, const be_mlp_tensors* exp_avg_sq, double* state,
+               double beta1, double beta2, double eps,
+               const double* losses, double* loss_log, int32_t log_rows, void* stream);
+
 /* ---- A2C targets: the batched finish_episode (examples/ball_cnn_ac3.py:222-246) ----
  * From a recorded rollout of `steps` rows of ctx's N envs -- contiguous (steps, N) device
  * arrays: rewards f64, dones u8 0/1 (what be_out.done and the rollouts write), values f32 or
