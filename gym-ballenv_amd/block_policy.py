@@ -37,6 +37,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _abi
+from .optim import HipOptim, is_f32
+from .rollout import GraphLoop, RolloutTrainer, a2c_targets, capture_steps
 
 BLOCKS = 29                      # prep_state2's row: 4 quadrant + 5 x 5 blocks
 # be_mlp_act's work split (csrc/mlp_policy.hip): a persistent grid of one workgroup per compute unit,
@@ -240,17 +242,7 @@ class BlockRollout:
     def capture(self, chunk: int = 250, stream: Optional[torch.cuda.Stream] = None) -> None:
         """Record the T steps into HIP graphs of ``chunk`` steps each (stream: the stream to capture
         on; default a new one from torch's pool)."""
-        dev = self.env.device
-        cap = torch.cuda.Stream(dev) if stream is None else stream
-        self._graphs = []
-        for c0 in range(0, self.T, max(1, int(chunk))):
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=cap):
-                sp = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-                for t in range(c0, min(self.T, c0 + max(1, int(chunk)))):
-                    self.step(t, sp)
-            self._graphs.append(g)
-        torch.cuda.synchronize(dev)
+        self._graphs = capture_steps(self.step, self.T, chunk, self.env.device, stream)
 
     def run(self) -> None:
         """Replay the captured horizon (capture() first)."""
@@ -352,14 +344,11 @@ class BlockGrad:
 
     def _params(self):
         ps = dict(self.policy.named_parameters())
-        ws = []
-        for k in self._names:
-            w = ps[k].detach()
-            if w.dtype != torch.float32 or not w.is_contiguous() or w.device != self.env.device or \
-                    w.shape != self.grads[k].shape:
+        ws = [ps[k].detach() for k in self._names]
+        for k, w in zip(self._names, ws):
+            if not is_f32(w, self.grads[k].shape, self.env.device):
                 raise ValueError(f"policy parameter {k} must be a contiguous f32 tensor of the shape BlockGrad was "
                                  "made for, on the env's device")
-            ws.append(w)
         return ws
 
     def __call__(self, blocks: torch.Tensor, actions: torch.Tensor, coef: Optional[torch.Tensor] = None,
@@ -408,7 +397,7 @@ class BlockGrad:
                 prm.grad.copy_(self.grads[k])
 
 
-class HipBlockOptim:
+class HipBlockOptim(HipOptim):
     """``be_mlp_opt`` bound to one ``HipBlockPolicy`` and its ``BlockPolicy`` module: ``torch.optim.Adam``
     (kind="adam": weight_decay=0, amsgrad=False, maximize=False -- ball_env_reinforce.py:196) or
     ``torch.optim.SGD`` (kind="sgd": momentum=0, weight_decay=0, no Nesterov -- train_supervise.py:75) on the
@@ -419,159 +408,23 @@ class HipBlockOptim:
 
     Owns the moments (adam: ``exp_avg`` / ``exp_avg_sq``, keyed like ``policy.state_dict()``), the device
     ``state`` [t, beta1^t, beta2^t, lr] and, with ``log_rows`` > 0, a (log_rows, 2) f64 ``loss_log``
-    ring: the step that starts at count t copies the ``losses`` it is given into row t % log_rows.
-    Nothing is allocated per call and nothing synchronises, so a step can be graph-captured; the
-    learning rate lives on the device, so a captured step follows ``opt.lr = ...``."""
+    ring: the step that starts at count t copies the ``losses`` it is given (the 2 f64 of
+    ``BlockGrad.losses``) into row t % log_rows.  Nothing is allocated per call and nothing synchronises,
+    so a step can be graph-captured; the learning rate lives on the device, so a captured step follows
+    ``opt.lr = ...``.  ``step``, ``state_dict`` and the rest: ``HipOptim`` (optim.py)."""
 
-    KINDS = {"adam": _abi.MLP_OPT_ADAM, "sgd": _abi.MLP_OPT_SGD}
+    KINDS = {"adam": (_abi.MLP_OPT_ADAM,), "sgd": (_abi.MLP_OPT_SGD,)}
+    LOSS_WIDTH = 2
+    STRUCT = _abi.BeMlpTensors
+    ON, MODULE = "HipBlockPolicy", "a BlockPolicy module of the HipBlockPolicy's layer count"
 
     def __init__(self, hip_block_policy: HipBlockPolicy, policy: BlockPolicy, kind: str = "adam", lr: float = 1e-2,
                  betas=(0.9, 0.999), eps: float = 1e-8, log_rows: int = 0):
-        if kind not in self.KINDS:
-            raise ValueError("kind must be 'adam' or 'sgd'")
-        self.hp, self.policy, self.kind = hip_block_policy, policy, kind
-        self.env = env = hip_block_policy.env
-        self._lib = _abi.lib()
-        dev = env.device
         hp = hip_block_policy
         h1, h2, A = hp.hidden1, hp.hidden2, hp.num_actions
         shapes = [(h1, BLOCKS), (h1,)] + ([(h2, h1), (h2,), (A, h2), (A,)] if hp.layers == 3 else [(A, h1), (A,)])
-        self._names = [f"affine{i + 1}.{w}" for i in range(hp.layers) for w in ("weight", "bias")]
-        self._shapes = dict(zip(self._names, shapes))
-        self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
-        if not (0.0 <= self.betas[0] < 1.0 and 0.0 <= self.betas[1] < 1.0) or self.eps < 0.0 or lr < 0.0:
-            raise ValueError("HipBlockOptim needs betas in [0, 1), eps >= 0 and lr >= 0")
-        self._params()                      # ValueError for a module this HipBlockPolicy was not made for
-        self.exp_avg = self.exp_avg_sq = self._m = self._v = None
-        if kind == "adam":
-            self.exp_avg = {k: torch.zeros(s, dtype=torch.float32, device=dev) for k, s in self._shapes.items()}
-            self.exp_avg_sq = {k: torch.zeros(s, dtype=torch.float32, device=dev) for k, s in self._shapes.items()}
-            self._m, self._v = self._tensors(self.exp_avg), self._tensors(self.exp_avg_sq)
-        self._lr = float(lr)
-        self.state = torch.tensor([0.0, 1.0, 1.0, self._lr], dtype=torch.float64, device=dev)
-        self.loss_log = torch.zeros(int(log_rows), 2, dtype=torch.float64, device=dev) if log_rows > 0 else None
-        self._keep = None
-
-    def _tensors(self, d) -> "_abi.BeMlpTensors":
-        ptrs = [d[k].data_ptr() for k in self._names]
-        return _abi.BeMlpTensors(*ptrs, *([None] * (6 - len(ptrs))))
-
-    def _check(self, what: str, k: str, x) -> torch.Tensor:
-        if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or not x.is_contiguous() or \
-                x.device != self.env.device or tuple(x.shape) != self._shapes[k]:
-            raise ValueError(f"{what} {k} must be a contiguous f32 tensor of shape {self._shapes[k]} on the "
-                             "HipBlockPolicy's device")
-        return x
-
-    def _params(self):
-        ps = dict(self.policy.named_parameters())
-        if set(ps) != set(self._names):
-            raise ValueError("HipBlockOptim needs a BlockPolicy module of the HipBlockPolicy's layer count")
-        return {k: self._check("policy parameter", k, ps[k].detach()) for k in self._names}
-
-    def step(self, grads=None, losses: Optional[torch.Tensor] = None) -> None:
-        """One optimiser step and the re-pack, asynchronous on the caller's current stream.
-        grads: ``BlockGrad.grads`` (a dict keyed like ``policy.state_dict()``), default: the parameters'
-        ``.grad``.  losses: the 2 f64 of ``BlockGrad.losses`` on the device, logged if there is a ``loss_log``."""
-        ws = self._params()
-        if grads is None:
-            ps = dict(self.policy.named_parameters())
-            if any(ps[k].grad is None for k in self._names):
-                raise ValueError("HipBlockOptim.step() without grads= needs every parameter's .grad")
-            gs = {k: self._check("gradient of", k, ps[k].grad) for k in self._names}
-        else:
-            gs = {k: self._check("gradient of", k, grads[k]) for k in self._names}
-        lp = gp = None
-        if losses is not None and self.loss_log is not None:
-            if losses.dtype != torch.float64 or losses.numel() != 2 or not losses.is_contiguous() or \
-                    losses.device != self.env.device:
-                raise ValueError("losses must be 2 contiguous f64 on the HipBlockPolicy's device")
-            lp, gp = losses.data_ptr(), self.loss_log.data_ptr()
-        w, g = self._tensors(ws), self._tensors(gs)
-        rc = self._lib.be_mlp_opt(self.hp._h, self.KINDS[self.kind], C.byref(w), C.byref(g),
-                                  None if self._m is None else C.byref(self._m),
-                                  None if self._v is None else C.byref(self._v), self.state.data_ptr(),
-                                  self.betas[0], self.betas[1], self.eps, lp, gp,
-                                  0 if gp is None else self.loss_log.shape[0], self.env._stream())
-        if rc:
-            _abi.check(rc, self.env._ctx)
-        self._keep = (ws, gs, losses)       # alive until the kernels have run
-
-    def zero_grad(self, set_to_none: bool = True) -> None:
-        self.policy.zero_grad(set_to_none=set_to_none)
-
-    @property
-    def lr(self) -> float:
-        return self._lr
-
-    @lr.setter
-    def lr(self, value: float) -> None:
-        self._lr = float(value)
-        self.state[3:].fill_(self._lr)      # stream-ordered: steps enqueued earlier keep the old rate
-
-    def step_count(self) -> int:
-        """Steps taken so far (synchronises)."""
-        return int(self.state[0].item())
-
-    def _torch_optim(self):
-        if self.kind == "adam":
-            return torch.optim.Adam(self.policy.parameters(), lr=self._lr, betas=self.betas, eps=self.eps)
-        return torch.optim.SGD(self.policy.parameters(), lr=self._lr)
-
-    def state_dict(self) -> dict:
-        """``torch.optim.Adam.state_dict()``'s (resp. ``torch.optim.SGD``'s) format, parameters in
-        ``policy.parameters()`` order, so the torch optimiser's ``load_state_dict(...)`` continues this run
-        (synchronises).  Plain SGD keeps no per-parameter state, so its ``state`` is empty and the step count
-        (which only picks the loss log's row) does not travel."""
-        state = {}
-        if self.kind == "adam":
-            t = self.step_count()
-            if t > 0:
-                state = {i: {"step": torch.tensor(float(t)), "exp_avg": self.exp_avg[k].clone(),
-                             "exp_avg_sq": self.exp_avg_sq[k].clone()} for i, k in enumerate(self._names)}
-        return {"state": state, "param_groups": self._torch_optim().state_dict()["param_groups"]}
-
-    def load_state_dict(self, sd: dict) -> None:
-        """From ``state_dict()`` of a HipBlockOptim of this kind or of the torch optimiser over
-        ``policy.parameters()``.  adam: beta^t is rebuilt by the repeated f64 product the device runs, so a
-        round trip continues bit for bit.  sgd: the learning rate is all there is; the step count stays."""
-        from .rollout import _beta_powers
-        n = len(self._names)
-        if len(sd["param_groups"]) != 1 or len(sd["param_groups"][0]["params"]) != n:
-            raise ValueError(f"HipBlockOptim needs one parameter group over the {n} BlockPolicy parameters")
-        grp, st = sd["param_groups"][0], sd["state"]
-        if grp.get("weight_decay", 0) != 0 or grp.get("maximize", False):
-            raise ValueError("HipBlockOptim has no weight_decay or maximize")
-        if self.kind == "sgd":
-            if "betas" in grp:
-                raise ValueError("this HipBlockOptim is kind='sgd': not an SGD state_dict")
-            if grp.get("momentum", 0) != 0 or grp.get("dampening", 0) != 0 or grp.get("nesterov", False):
-                raise ValueError("HipBlockOptim's SGD has no momentum, dampening or Nesterov")
-            if any(s.get("momentum_buffer") is not None for s in st.values()):
-                raise ValueError("HipBlockOptim's SGD has no momentum buffers")
-            self.lr = float(grp["lr"])
-            return
-        if "betas" not in grp or "eps" not in grp:
-            raise ValueError("this HipBlockOptim is kind='adam': not an Adam state_dict")
-        if grp.get("amsgrad", False):
-            raise ValueError("HipBlockOptim has no amsgrad")
-        steps = {int(float(st[i]["step"])) for i in st}
-        if st and (len(st) != n or len(steps) != 1):
-            raise ValueError("HipBlockOptim needs the state of every parameter at one common step")
-        t = steps.pop() if st else 0
-        for j, k in enumerate(self._names):
-            i = grp["params"][j]
-            for mine, key in ((self.exp_avg, "exp_avg"), (self.exp_avg_sq, "exp_avg_sq")):
-                if st:
-                    if tuple(st[i][key].shape) != self._shapes[k]:
-                        raise ValueError(f"{key} of {k} has the wrong shape")
-                    mine[k].copy_(st[i][key])
-                else:
-                    mine[k].zero_()
-        self.betas, self.eps, self._lr = (float(grp["betas"][0]), float(grp["betas"][1])), float(grp["eps"]), \
-            float(grp["lr"])
-        p1, p2 = _beta_powers(t, self.betas)
-        self.state.copy_(torch.tensor([float(t), p1, p2, self._lr], dtype=torch.float64))
+        names = [f"affine{i + 1}.{w}" for i in range(hp.layers) for w in ("weight", "bias")]
+        super().__init__(hp, policy, _abi.lib().be_mlp_opt, names, shapes, kind, lr, betas, eps, log_rows)
 
 
 def _check_block_optim(optimizer, hp, policy) -> bool:
@@ -604,7 +457,6 @@ def reinforce_update(rollout: BlockRollout, optimizer, gamma: float = 0.99, targ
     if grads == "hip":
         if targets != "hip":
             raise ValueError("grads='hip' needs targets='hip'")
-        from .rollout import a2c_targets
         t = a2c_targets(rollout.env, rollout.rewards, rollout.dones, None, gamma, with_returns=False)
         bg = getattr(rollout, "_block_grad", None)
         if bg is None or bg.policy is not rollout.policy:
@@ -620,7 +472,6 @@ def reinforce_update(rollout: BlockRollout, optimizer, gamma: float = 0.99, targ
         return loss
     tg = None
     if targets == "hip":
-        from .rollout import a2c_targets
         t = a2c_targets(rollout.env, rollout.rewards, rollout.dones, None, gamma, with_returns=False)
         tg = (t.returns_norm, t.valid)
     loss = reinforce_losses(rollout.policy, rollout.blocks, rollout.actions, rollout.rewards, rollout.dones, gamma,
@@ -681,16 +532,7 @@ def supervised_update(policy: BlockPolicy, blocks: torch.Tensor, labels: torch.T
     return float(loss.detach())
 
 
-def _unrolled_log(opt: HipBlockOptim, who: str) -> torch.Tensor:
-    log = opt.loss_log
-    if log is None:
-        raise ValueError(f"{who}(log_rows=...) keeps the loss log")
-    t, rows = opt.step_count(), log.shape[0]
-    out = log[:t] if t <= rows else torch.roll(log, -(t % rows), 0)
-    return out.cpu()
-
-
-class BlockTrainer:
+class BlockTrainer(RolloutTrainer):
     """The REINFORCE training loop (ball_env_reinforce.py:88-108, :196-230) with no host round trip between
     two rollouts: per iteration ``BlockRollout`` -> ``a2c_targets_into`` (no values) -> ``BlockGrad``
     ("reinforce", scale 1) -> ``HipBlockOptim("adam").step`` (which re-packs the policy), all enqueued on
@@ -699,66 +541,22 @@ class BlockTrainer:
     Owns a ``BlockRollout(record_obs=True)``, preallocated ``A2CTargets`` (returns_norm and valid), a
     ``BlockGrad`` and a ``HipBlockOptim`` (``.opt``; ``log_rows`` sizes its loss log).  ``capture()`` records
     the rollout (``BlockRollout.capture``, ``chunk`` steps per graph) and the update half into HIP graphs,
-    linear chains on one stream, which ``train()`` then replays."""
+    linear chains on one stream, which ``train()`` then replays.
+    ``losses()``: the loss log as (iterations, 2) f64 on the host -- the REINFORCE loss and the active rows
+    of each iteration, the last ``log_rows`` of them once the ring has wrapped (synchronises)."""
 
     def __init__(self, env, policy: BlockPolicy, horizon: int, gamma: float = 0.99, lr: float = 1e-2,
                  betas=(0.9, 0.999), eps: float = 1e-8, seed: int = 0x5E1EC7, log_rows: int = 0, chunk: int = 250):
-        from .rollout import A2CTargets
-        self.env, self.policy, self.gamma, self.chunk = env, policy, float(gamma), int(chunk)
-        self.rollout = BlockRollout(env, policy, horizon, record_obs=True, seed=seed)
-        T, N, dev = self.rollout.T, env.num_envs, env.device
-        self.targets = A2CTargets(torch.zeros(T, N, dtype=torch.float32, device=dev), None,
-                                  torch.zeros(T, N, dtype=torch.uint8, device=dev), None)
+        super().__init__(env, policy, BlockRollout(env, policy, horizon, record_obs=True, seed=seed), gamma)
+        self.chunk = self.GRAPH_CHUNK = int(chunk)
         self.grad = BlockGrad(env, policy)
         self.opt = HipBlockOptim(self.rollout.hp, policy, "adam", lr=lr, betas=betas, eps=eps, log_rows=log_rows)
-        self._eps = float(np.finfo(np.float32).eps)
-        self._graph = None
 
-    def update(self) -> None:
-        """The update half on the recorded rollout: targets, gradients, Adam step + re-pack."""
-        from .rollout import a2c_targets_into
-        ro = self.rollout
-        a2c_targets_into(self.env, ro.rewards, ro.dones, None, self.gamma, self._eps, None, self.targets)
-        g = self.grad(ro.blocks, ro.actions, self.targets.returns_norm, self.targets.valid, "reinforce", 1.0)
-        self.opt.step(g, self.grad.losses)
-
-    def capture(self, stream: Optional[torch.cuda.Stream] = None) -> None:
-        """Record the rollout and ``update()`` into HIP graphs.  stream: the stream to capture on; default
-        a new one from torch's pool."""
-        dev = self.env.device
-        cap = torch.cuda.Stream(dev) if stream is None else stream
-        self.rollout.capture(chunk=self.chunk, stream=cap)
-        torch.cuda.synchronize(dev)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, stream=cap):
-            self.update()
-        torch.cuda.synchronize(dev)
-        self._graph = g
-
-    def train(self, iterations: int) -> None:
-        """``iterations`` times rollout + update, enqueued without a synchronise."""
-        ro = self.rollout
-        for _ in range(int(iterations)):
-            if ro._graphs:
-                ro.run()
-            else:
-                ro.run_eager()
-            if self._graph is not None:
-                self._graph.replay()
-            else:
-                self.update()
-
-    def losses(self) -> torch.Tensor:
-        """The loss log as (iterations, 2) f64 on the host -- the REINFORCE loss and the active rows of each
-        iteration, the last ``log_rows`` of them once the ring has wrapped (synchronises)."""
-        return _unrolled_log(self.opt, "BlockTrainer")
-
-    def close(self) -> None:
-        self._graph = None
-        self.rollout.close()
+    def _grads(self, ro, tg):
+        return self.grad(ro.blocks, ro.actions, tg.returns_norm, tg.valid, "reinforce", 1.0), self.grad.losses
 
 
-class SupervisedTrainer:
+class SupervisedTrainer(GraphLoop):
     """The supervised loop of examples/train_supervise.py:80-101 on device-resident data, with no host round
     trip: per minibatch ``BlockGrad`` ("xent", scale 1 / batch) -> ``HipBlockOptim("sgd").step``.
 
@@ -767,7 +565,9 @@ class SupervisedTrainer:
     of 186).  The minibatches are contiguous views in the data's order (the reference does not shuffle), so
     nothing is copied.  Owns a ``HipBlockPolicy`` (``.hp``: it acts with the weights of the last step), a
     ``BlockGrad`` and the ``HipBlockOptim`` (``.opt``).  ``capture()`` records one epoch as one HIP graph, a
-    linear chain, which ``train()`` then replays."""
+    linear chain, which ``train()`` then replays.
+    ``losses()``: the loss log as (steps, 2) f64 on the host -- each minibatch's mean cross-entropy and its
+    row count, the last ``log_rows`` of them once the ring has wrapped (synchronises)."""
 
     def __init__(self, env, policy: BlockPolicy, blocks: torch.Tensor, labels: torch.Tensor, batch_size: int = 200,
                  lr: float = 1e-2, log_rows: int = 0):
@@ -782,44 +582,20 @@ class SupervisedTrainer:
             raise ValueError("batch_size must be >= 1")
         self.env, self.policy, self.blocks, self.labels = env, policy, blocks, labels
         self.batch_size = int(batch_size)
-        self.hp = HipBlockPolicy(env, policy)
+        self.hp = self._closes = HipBlockPolicy(env, policy)
         self.grad = BlockGrad(env, policy)
         self.opt = HipBlockOptim(self.hp, policy, "sgd", lr=lr, log_rows=log_rows)
         rows = int(blocks.shape[0])
         self._batches = [(blocks[i:j], labels[i:j], 1.0 / (j - i))
                          for i in range(0, rows, self.batch_size) for j in (min(rows, i + self.batch_size),)]
-        self._graph = None
 
     def epoch(self) -> None:
         """One pass over the minibatches, enqueued on the caller's current stream."""
         for b, l, scale in self._batches:
             self.opt.step(self.grad(b, l, None, None, "xent", scale), self.grad.losses)
 
-    def capture(self, stream: Optional[torch.cuda.Stream] = None) -> None:
-        """Record ``epoch()`` into one HIP graph.  stream: the stream to capture on; default a new one
-        from torch's pool."""
-        dev = self.env.device
-        cap = torch.cuda.Stream(dev) if stream is None else stream
-        torch.cuda.synchronize(dev)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, stream=cap):
-            self.epoch()
-        torch.cuda.synchronize(dev)
-        self._graph = g
+    _pass = epoch
 
     def train(self, epochs: int) -> None:
         """``epochs`` passes, enqueued without a synchronise."""
-        for _ in range(int(epochs)):
-            if self._graph is not None:
-                self._graph.replay()
-            else:
-                self.epoch()
-
-    def losses(self) -> torch.Tensor:
-        """The loss log as (steps, 2) f64 on the host -- each minibatch's mean cross-entropy and its row
-        count, the last ``log_rows`` of them once the ring has wrapped (synchronises)."""
-        return _unrolled_log(self.opt, "SupervisedTrainer")
-
-    def close(self) -> None:
-        self._graph = None
-        self.hp.close()
+        super().train(epochs)

@@ -19,11 +19,14 @@ object) and linked into one shared library:
   csrc/a2c_grad.hip A2C losses and Policy gradients of recorded rows (f32 MFMAs; no VGPR_MFMA:
                     its accumulators live for the whole kernel, and with them in VGPRs the W = 10
                     instance measured 14 % slower, W = 5 the same: profiles/a2c_grad_ab.json)
-  csrc/a2c_adam.hip the Adam step on the six Policy tensors and the re-pack of the policy image (f64
-                    operations with -ffp-contract=off, as every unit: the pinned arithmetic has no FMA)
+  csrc/optim_core.h the pinned optimiser arithmetic, once: an Adam step's constants, one element's Adam
+                    and SGD update (f64 operations with -ffp-contract=off, as every unit: no FMA)
+  csrc/a2c_adam.hip the Adam step on the six Policy tensors and the re-pack of the policy image
+                    (optim_core.h); and the one-thread state kernel both optimiser entries launch
   csrc/mlp_policy.hip select_action of the REINFORCE / supervised block-count MLP (f32 MFMAs) straight
                     from the env state; shares blocks_core.h (prep_state2 of one env) with features.hip;
-                    and next to its pack kernel the Adam / SGD step fused with the re-pack (be_mlp_opt)
+                    and next to its pack kernel the Adam / SGD step fused with the re-pack (be_mlp_opt,
+                    optim_core.h)
   csrc/mlp_grad.hip the block-count MLP's REINFORCE / cross-entropy losses and gradients of recorded rows
                     (f32 MFMAs; no VGPR_MFMA, for a2c_grad.hip's reason: the gradient accumulators live
                     for the whole kernel, the AGPR half of the register file is where they belong)
@@ -55,7 +58,7 @@ UNITS = {"ballenv.hip": [*VGPR_MFMA, *KARG_PRELOAD], "abi.hip": [], "policy.hip"
          "features.hip": [], "board.hip": [], "a2c.hip": [], "a2c_grad.hip": [], "a2c_adam.hip": [],
          "mlp_policy.hip": [], "mlp_grad.hip": []}
 HEADERS = [HDR, *(os.path.join(CSRC, h) for h in ("philox.h", "internal.h", "host_logic.h", "pool_layout.h", "policy_core.h", "blocks_core.h", "diag.h",
-                                              "step_types.h"))]
+                                              "step_types.h", "optim_core.h"))]
 
 
 def _stale(out, deps):

@@ -17,9 +17,10 @@
 //                      planes into the fragment layout, bq_m and the row's NO scaled head entries
 //                      through the helpers the pack kernel uses (policy_core.h).  Rows m >= H write
 //                      the zeros the pack kernel writes.  No wave reads what another writes.
-//   a2c_adam_advance   one thread: copies the losses into row (t mod rows) of the log, then advances
+//   optim_advance      one wave: copies the losses into row (t mod rows) of the log, then advances
 //                      the state [t, beta1^t, beta2^t, lr].  Every wave of the kernel before it read
 //                      the state as it was before the call; stream order is the only ordering needed.
+//                      Defined here for be_mlp_opt as well (be_internal_optim_advance, internal.h).
 //   policy_kernel      the table pass over the four empty-window observations, as in be_policy_load
 //                      (be_internal_policy_table).
 #include <hip/hip_runtime.h>
@@ -28,7 +29,9 @@
 #include <stdint.h>
 
 #include "ballenv.h"
+#include "host_logic.h"
 #include "internal.h"
+#include "optim_core.h"
 #include "policy_core.h"
 
 namespace {
@@ -48,26 +51,13 @@ struct AParams {
   int32_t H, F, A;
 };
 
-struct Step { double beta1, beta2, omb1, omb2, eps, bc2s, ss; };
-
-// One element: the pinned arithmetic (no FMA: the unit is built with -ffp-contract=off).  Returns w'.
-__device__ __forceinline__ float adam_elem(const Step& c, const float* g, float* m, float* v, float* w, int64_t i) {
-  const double gd = (double)g[i];
-  const float m1 = (float)(c.beta1 * (double)m[i] + c.omb1 * gd);
-  const float v1 = (float)(c.beta2 * (double)v[i] + (c.omb2 * gd) * gd);
-  const float w1 = (float)((double)w[i] - c.ss * ((double)m1 / (sqrt((double)v1) / c.bc2s + c.eps)));
-  m[i] = m1; v[i] = v1; w[i] = w1;
-  return w1;
-}
-
 __global__ __launch_bounds__(THREADS) void a2c_adam_kernel(AParams p) {
   const PolLayout& L = p.L;
   const int lane = (int)threadIdx.x & 63;
   const int m = __builtin_amdgcn_readfirstlane((int)blockIdx.x * ROWS_PER_WG + ((int)threadIdx.x >> 6));
   const int rows = 16 * L.HT, H = p.H, F = p.F, A = p.A, NO = L.NO;
   if (m > rows) return;
-  const double p1 = p.state[1] * p.beta1, p2 = p.state[2] * p.beta2, lr = p.state[3];
-  const Step c{p.beta1, p.beta2, 1.0 - p.beta1, 1.0 - p.beta2, p.eps, sqrt(1.0 - p2), lr / (1.0 - p1)};
+  const AdamStep c = adam_step(p.state, p.beta1, p.beta2, p.eps);
   const bool is_act = lane < A, is_val = lane == NO - 1;     // this lane's head output, if any
 
   if (m == rows) {           // the head biases: action o in lane o, the value bias in lane NO - 1
@@ -112,17 +102,22 @@ __global__ __launch_bounds__(THREADS) void a2c_adam_kernel(AParams p) {
   if (lane < NO) pol_store_head(p.img, L, m, lane, (double)hw, s);
 }
 
-__global__ void a2c_adam_advance(double* state, double beta1, double beta2, const double* losses, double* loss_log,
-                                 int32_t log_rows) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+// One wave, behind an update kernel on the stream: lane k < width copies loss k into row (t mod rows) of
+// the log (one load and one store in flight for the whole row), then lane 0 advances the state
+// (powers == 0, plain SGD: the step count alone).  Every lane has its t before lane 0 stores t + 1: the
+// load is one instruction of the wave, and the stored value depends on it.
+__global__ __launch_bounds__(64) void optim_advance(double* state, int32_t powers, double beta1, double beta2,
+                                                    const double* losses, double* loss_log, int32_t width,
+                                                    int32_t log_rows) {
+  const int k = (int)threadIdx.x;
   const double t = state[0];
-  if (loss_log) {
-    double* row = loss_log + 3 * ((int64_t)t % log_rows);
-    row[0] = losses[0]; row[1] = losses[1]; row[2] = losses[2];
-  }
+  if (loss_log && k < width) loss_log[width * ((int64_t)t % log_rows) + k] = losses[k];
+  if (k != 0) return;
   state[0] = t + 1.0;
-  state[1] = state[1] * beta1;
-  state[2] = state[2] * beta2;
+  if (powers) {
+    state[1] = state[1] * beta1;
+    state[2] = state[2] * beta2;
+  }
 }
 
 // the first NULL or misaligned pointer of a tensor set, as "<set>-><field>", or nullptr
@@ -149,6 +144,13 @@ Six six(const be_a2c_tensors* t) {
 
 }  // namespace
 
+int be_internal_optim_advance(char* err, double* state, bool powers, double beta1, double beta2, const double* losses,
+                              double* loss_log, int32_t width, int32_t log_rows, void* stream) {
+  hipLaunchKernelGGL(optim_advance, dim3(1), dim3(64), 0, (hipStream_t)stream, state, (int32_t)powers, beta1, beta2,
+                     losses, loss_log, width, log_rows);
+  return be_launched(err);
+}
+
 extern "C" {
 
 int be_a2c_adam(be_policy* pol, const be_a2c_tensors* params, const be_a2c_tensors* grads,
@@ -167,16 +169,8 @@ int be_a2c_adam(be_policy* pol, const be_a2c_tensors* params, const be_a2c_tenso
   for (const auto& s : sets)
     if (const char* name = bad_field(s.t, s.names))
       return be_fail(err, BE_E_INVALID, "be_a2c_adam: %s is NULL or not 4-byte aligned", name);
-  if (!state || ((uintptr_t)state & 7))
-    return be_ctx_fail(ctx, BE_E_INVALID, "be_a2c_adam: state is NULL or not 8-byte aligned");
-  if (!(beta1 >= 0.0 && beta1 < 1.0)) return be_ctx_fail(ctx, BE_E_INVALID, "be_a2c_adam: beta1 must be in [0, 1)");
-  if (!(beta2 >= 0.0 && beta2 < 1.0)) return be_ctx_fail(ctx, BE_E_INVALID, "be_a2c_adam: beta2 must be in [0, 1)");
-  if (!(eps >= 0.0)) return be_ctx_fail(ctx, BE_E_INVALID, "be_a2c_adam: eps must be >= 0");
-  if ((losses != nullptr) != (loss_log != nullptr))
-    return be_ctx_fail(ctx, BE_E_INVALID, "be_a2c_adam: losses and loss_log go together (both or neither)");
-  if (((uintptr_t)losses & 7) || ((uintptr_t)loss_log & 7))
-    return be_ctx_fail(ctx, BE_E_INVALID, "be_a2c_adam: losses / loss_log is not 8-byte aligned");
-  if (loss_log && log_rows < 1) return be_ctx_fail(ctx, BE_E_INVALID, "be_a2c_adam: log_rows must be >= 1");
+  if (const char* msg = behost::optim_args_error(state, true, beta1, beta2, eps, losses, loss_log, log_rows))
+    return be_fail(err, BE_E_INVALID, "be_a2c_adam: %s", msg);
   BE_ENTER_DEVICE(err, pv.device);
   const AParams p{six(params), six(grads), six(exp_avg), six(exp_avg_sq), state, beta1, beta2, eps, pv.img,
                   pol_layout(pv.HT, pv.KS, pv.NO), pv.H, pv.F, pv.A};
@@ -185,8 +179,7 @@ int be_a2c_adam(be_policy* pol, const be_a2c_tensors* params, const be_a2c_tenso
   hipLaunchKernelGGL(a2c_adam_kernel, dim3((unsigned)((waves + ROWS_PER_WG - 1) / ROWS_PER_WG)), dim3(THREADS), 0, hs,
                      p);
   if (int rc = be_launched(err)) return rc;
-  hipLaunchKernelGGL(a2c_adam_advance, dim3(1), dim3(64), 0, hs, state, beta1, beta2, losses, loss_log, log_rows);
-  if (int rc = be_launched(err)) return rc;
+  if (int rc = be_internal_optim_advance(err, state, true, beta1, beta2, losses, loss_log, 3, log_rows, stream)) return rc;
   return be_internal_policy_table(pol, stream);
 }
 

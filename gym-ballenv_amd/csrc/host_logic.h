@@ -107,6 +107,23 @@ inline be_out be_out_at(const be_out& out, int64_t s, int64_t N, int64_t F) {
   return o;
 }
 
+// The optimiser arguments be_a2c_adam and be_mlp_opt share, checked in this order: the state, the Adam
+// constants (adam == false, plain SGD, has none), the loss log.  NULL: fine, else the message's tail,
+// which the entry point puts behind its own name.
+inline const char* optim_args_error(const double* state, bool adam, double beta1, double beta2, double eps,
+                                    const double* losses, const double* loss_log, int32_t log_rows) {
+  if (!state || ((uintptr_t)state & 7)) return "state is NULL or not 8-byte aligned";
+  if (adam) {
+    if (!(beta1 >= 0.0 && beta1 < 1.0)) return "beta1 must be in [0, 1)";
+    if (!(beta2 >= 0.0 && beta2 < 1.0)) return "beta2 must be in [0, 1)";
+    if (!(eps >= 0.0)) return "eps must be >= 0";
+  }
+  if ((losses != nullptr) != (loss_log != nullptr)) return "losses and loss_log go together (both or neither)";
+  if (((uintptr_t)losses & 7) || ((uintptr_t)loss_log & 7)) return "losses / loss_log is not 8-byte aligned";
+  if (loss_log && log_rows < 1) return "log_rows must be >= 1";
+  return nullptr;
+}
+
 // be_mlp_grad's argument checks that need no device (mlp_grad.hip): the block MLP's shape against
 // be_mlp_create's bounds and w3 / b3 against the layer count.  NULL: fine, else the message.
 inline const char* mlp_grad_shape_error(int layers, int hidden1, int hidden2, int num_actions) {

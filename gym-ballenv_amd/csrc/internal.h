@@ -104,6 +104,15 @@ __attribute__((visibility("hidden"))) be_policy_view be_policy_get(const be_poli
 // caller has entered the policy's device.  BE_OK or an error code recorded in the ctx.
 __attribute__((visibility("hidden"))) int be_internal_policy_table(be_policy* pol, void* stream);
 
+// The state kernel behind an optimiser's update kernel (be_a2c_adam, be_mlp_opt; defined in a2c_adam.hip):
+// one wave copies the `width` <= 64 losses into row (t mod log_rows) of loss_log (if there is one), then
+// advances state [t, beta1^t, beta2^t, lr] -- the step count alone unless `powers`.  One dim3(1), dim3(64)
+// launch on `stream`; the caller has checked the arguments and entered the device.  BE_OK or a HIP error
+// recorded in err.
+__attribute__((visibility("hidden"))) int be_internal_optim_advance(char* err, double* state, bool powers, double beta1,
+                                                                    double beta2, const double* losses, double* loss_log,
+                                                                    int32_t width, int32_t log_rows, void* stream);
+
 // fused config-5 rollout (be_policy_rollout -> rollout_kernel with the policy in the loop)
 struct be_pol_rollout_args {
   const uint8_t* img;          // packed Policy(W) image (device)

@@ -14,7 +14,8 @@
 //                 include/ballenv.h pins
 //   be_mlp_opt    two launches: optimizer.step() of both training loops (Adam, ball_env_reinforce.py:196;
 //                 SGD, train_supervise.py:75) on the state_dict tensors in place, fused with be_mlp_load's
-//                 pack of the new weights; then the one-thread state kernel
+//                 pack of the new weights; then the one-wave state kernel it shares with
+//                 be_a2c_adam (be_internal_optim_advance)
 //
 // Every product runs on v_mfma_f32_16x16x4_f32 (an exact f32 fma chain) as D = W . x^T: the
 // weights are the A operand (row = output unit), a tile of 16 envs the B operand (column = env),
@@ -43,7 +44,9 @@
 
 #include "ballenv.h"
 #include "blocks_core.h"
+#include "host_logic.h"
 #include "internal.h"
+#include "optim_core.h"
 #include "philox.h"
 #include "policy_core.h"
 
@@ -153,8 +156,6 @@ struct OParams {
   int32_t e0, e1, e2, e3, e4, e5;      // the running ends of the six tensors in the element order
 };
 
-struct OStep { double beta1, beta2, omb1, omb2, eps, bc2s, ss; };
-
 template <int KIND>
 __global__ __launch_bounds__(256) void mlp_opt_kernel(OParams p) {
   const MlpLayout& L = p.L;
@@ -197,38 +198,11 @@ __global__ __launch_bounds__(256) void mlp_opt_kernel(OParams p) {
     dst = L.b3 + j;
     w = p.w.bl; g = p.g.bl; m1p = p.m.bl; m2p = p.v.bl;
   }
-  // the pinned arithmetic of include/ballenv.h (no FMA: the unit is built with -ffp-contract=off)
-  const double gd = (double)g[j];
-  float wn;
-  if constexpr (KIND == BE_MLP_OPT_ADAM) {
-    const double p1 = p.state[1] * p.beta1, p2 = p.state[2] * p.beta2, lr = p.state[3];
-    const OStep c{p.beta1, p.beta2, 1.0 - p.beta1, 1.0 - p.beta2, p.eps, sqrt(1.0 - p2), lr / (1.0 - p1)};
-    const float m1 = (float)(c.beta1 * (double)m1p[j] + c.omb1 * gd);
-    const float v1 = (float)(c.beta2 * (double)m2p[j] + (c.omb2 * gd) * gd);
-    wn = (float)((double)w[j] - c.ss * ((double)m1 / (sqrt((double)v1) / c.bc2s + c.eps)));
-    m1p[j] = m1; m2p[j] = v1;
-  } else {
-    wn = (float)((double)w[j] - p.state[3] * gd);
-  }
-  w[j] = wn;
-  p.img[dst] = wn;
-}
-
-// One thread, behind the update kernel on the stream: the losses into row (t mod rows) of the log, then
-// the state's advance (SGD: the step count alone).
-__global__ void mlp_opt_advance(double* state, int32_t kind, double beta1, double beta2, const double* losses,
-                                double* loss_log, int32_t log_rows) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  const double t = state[0];
-  if (loss_log) {
-    double* row = loss_log + 2 * ((int64_t)t % log_rows);
-    row[0] = losses[0]; row[1] = losses[1];
-  }
-  state[0] = t + 1.0;
-  if (kind == BE_MLP_OPT_ADAM) {
-    state[1] = state[1] * beta1;
-    state[2] = state[2] * beta2;
-  }
+  // the pinned arithmetic of include/ballenv.h (optim_core.h)
+  if constexpr (KIND == BE_MLP_OPT_ADAM)
+    p.img[dst] = adam_elem(adam_step(p.state, p.beta1, p.beta2, p.eps), g, m1p, m2p, w, j);
+  else
+    p.img[dst] = sgd_elem(p.state[3], g, w, j);
 }
 
 // the first pointer of a tensor set that is NULL or misaligned where the layer count needs it, or set
@@ -531,18 +505,8 @@ int be_mlp_opt(be_mlp* m, int32_t kind, const be_mlp_tensors* params, const be_m
       return be_fail(err, BE_E_INVALID,
                      "be_mlp_opt: %s is NULL or not 4-byte aligned (w3 and b3: set with 3 layers, NULL with 2)", name);
   }
-  if (!state || ((uintptr_t)state & 7))
-    return be_ctx_fail(ctx, BE_E_INVALID, "be_mlp_opt: state is NULL or not 8-byte aligned");
-  if (adam) {
-    if (!(beta1 >= 0.0 && beta1 < 1.0)) return be_ctx_fail(ctx, BE_E_INVALID, "be_mlp_opt: beta1 must be in [0, 1)");
-    if (!(beta2 >= 0.0 && beta2 < 1.0)) return be_ctx_fail(ctx, BE_E_INVALID, "be_mlp_opt: beta2 must be in [0, 1)");
-    if (!(eps >= 0.0)) return be_ctx_fail(ctx, BE_E_INVALID, "be_mlp_opt: eps must be >= 0");
-  }
-  if ((losses != nullptr) != (loss_log != nullptr))
-    return be_ctx_fail(ctx, BE_E_INVALID, "be_mlp_opt: losses and loss_log go together (both or neither)");
-  if (((uintptr_t)losses & 7) || ((uintptr_t)loss_log & 7))
-    return be_ctx_fail(ctx, BE_E_INVALID, "be_mlp_opt: losses / loss_log is not 8-byte aligned");
-  if (loss_log && log_rows < 1) return be_ctx_fail(ctx, BE_E_INVALID, "be_mlp_opt: log_rows must be >= 1");
+  if (const char* msg = behost::optim_args_error(state, adam, beta1, beta2, eps, losses, loss_log, log_rows))
+    return be_fail(err, BE_E_INVALID, "be_mlp_opt: %s", msg);
   BE_ENTER_DEVICE(err, m->cv.device);
   OParams p{};
   p.w = mlp_six(params, m->layers); p.g = mlp_six(grads, m->layers);
@@ -561,8 +525,7 @@ int be_mlp_opt(be_mlp* m, int32_t kind, const be_mlp_tensors* params, const be_m
   if (adam) hipLaunchKernelGGL((mlp_opt_kernel<BE_MLP_OPT_ADAM>), grid, block, 0, hs, p);
   else hipLaunchKernelGGL((mlp_opt_kernel<BE_MLP_OPT_SGD>), grid, block, 0, hs, p);
   if (int rc = be_launched(err)) return rc;
-  hipLaunchKernelGGL(mlp_opt_advance, dim3(1), dim3(64), 0, hs, state, kind, beta1, beta2, losses, loss_log, log_rows);
-  if (int rc = be_launched(err)) return rc;
+  if (int rc = be_internal_optim_advance(err, state, adam, beta1, beta2, losses, loss_log, 2, log_rows, stream)) return rc;
   m->loaded = true;
   return BE_OK;
 }

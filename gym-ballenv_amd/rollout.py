@@ -29,7 +29,8 @@ return normalisation, policy + value losses) over all envs at once, so a
 training loop is rollout (HIP) -> update (torch autograd) -> re-pack (HIP).
 ``A2CGrad`` (``a2c_update(grads="hip")``) is the losses and ``loss.backward()``
 of that update in one HIP entry (``be_a2c_grad``), straight from the u8 record.
-``HipAdam`` is ``optimizer.step()`` and the re-pack in one HIP entry (``be_a2c_adam``), and
+``HipAdam`` is ``optimizer.step()`` and the re-pack in one HIP entry (``be_a2c_adam``; optim.py's
+``HipOptim`` is what it shares with the block policy's ``HipBlockOptim``), and
 ``A2CTrainer`` the loop rollout -> targets -> gradients -> Adam -> re-packed policy with no host
 round trip between two rollouts, its update half replayed as one HIP graph.
 """
@@ -41,6 +42,7 @@ from typing import NamedTuple, Optional
 import torch
 
 from . import _abi
+from .optim import HipOptim, _beta_powers, is_f32      # noqa: F401  (_beta_powers stays importable from here)
 from .policy import HipPolicy, Policy, torch_select_action
 
 
@@ -130,14 +132,11 @@ class A2CGrad:
 
     def _params(self):
         ps = dict(self.policy.named_parameters())
-        ws = []
-        for k in _PARAMS:
-            w = ps[k].detach()
-            if w.dtype != torch.float32 or not w.is_contiguous() or w.device != self.env.device or \
-                    w.shape != self.grads[k].shape:
+        ws = [ps[k].detach() for k in _PARAMS]
+        for k, w in zip(_PARAMS, ws):
+            if not is_f32(w, self.grads[k].shape, self.env.device):
                 raise ValueError(f"policy parameter {k} must be a contiguous f32 tensor of the shape A2CGrad was "
                                  "made for, on the env's device")
-            ws.append(w)
         return ws
 
     def __call__(self, obs: torch.Tensor, actions: torch.Tensor, returns_norm: torch.Tensor, valid: torch.Tensor):
@@ -177,17 +176,7 @@ class A2CGrad:
         return pl, vl, int(n)
 
 
-def _beta_powers(t: int, betas):
-    """(beta1^t, beta2^t) as be_a2c_adam's state holds them after t steps: the running f64 products,
-    one multiply per step (``beta ** t`` differs in the last bits)."""
-    p1 = p2 = 1.0
-    for _ in range(int(t)):
-        p1 *= float(betas[0])
-        p2 *= float(betas[1])
-    return p1, p2
-
-
-class HipAdam:
+class HipAdam(HipOptim):
     """``be_a2c_adam`` bound to one ``HipPolicy`` and its ``Policy`` module: ``torch.optim.Adam``
     (weight_decay=0, amsgrad=False, maximize=False) on the six parameters in place *and* the re-pack of
     the new weights into ``hip_policy``, in one asynchronous entry (include/ballenv.h pins the
@@ -196,126 +185,45 @@ class HipAdam:
 
     Owns the moments (``exp_avg`` / ``exp_avg_sq``, keyed like ``policy.state_dict()``), the device
     ``state`` [t, beta1^t, beta2^t, lr] and, with ``log_rows`` > 0, a (log_rows, 3) f64 ``loss_log``
-    ring: the step that starts at count t copies the ``losses`` it is given into row t % log_rows.
-    Nothing is allocated per call and nothing synchronises, so a step can be graph-captured; the
-    learning rate lives on the device, so a captured step follows ``opt.lr = ...``."""
+    ring: the step that starts at count t copies the ``losses`` it is given (the 3 f64 of ``A2CGrad``)
+    into row t % log_rows.  Nothing is allocated per call and nothing synchronises, so a step can be
+    graph-captured; the learning rate lives on the device, so a captured step follows ``opt.lr = ...``.
+    ``step``, ``state_dict`` and the rest: ``HipOptim`` (optim.py)."""
+
+    KINDS = {"adam": ()}
+    LOSS_WIDTH = 3
+    STRUCT = _abi.BeA2CTensors
+    ON, MODULE = "HipPolicy", "a Policy module (fc1, action_head, value_head)"
 
     def __init__(self, hip_policy: HipPolicy, policy: Policy, lr: float = 1e-3, betas=(0.9, 0.999),
                  eps: float = 1e-8, log_rows: int = 0):
-        self.hp, self.policy = hip_policy, policy
-        self.env = env = hip_policy.env
-        self._lib = _abi.lib()
-        dev = env.device
-        H, A, F = hip_policy.hidden, hip_policy.num_actions, env.obs_dim
-        self._shapes = dict(zip(_PARAMS, ((H, F), (H,), (A, H), (A,), (1, H), (1,))))
-        self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
-        if not (0.0 <= self.betas[0] < 1.0 and 0.0 <= self.betas[1] < 1.0) or self.eps < 0.0 or lr < 0.0:
-            raise ValueError("HipAdam needs betas in [0, 1), eps >= 0 and lr >= 0")
-        self._params()                      # ValueError for a module this HipPolicy was not made for
-        self.exp_avg = {k: torch.zeros(s, dtype=torch.float32, device=dev) for k, s in self._shapes.items()}
-        self.exp_avg_sq = {k: torch.zeros(s, dtype=torch.float32, device=dev) for k, s in self._shapes.items()}
-        self._lr = float(lr)
-        self.state = torch.tensor([0.0, 1.0, 1.0, self._lr], dtype=torch.float64, device=dev)
-        self.loss_log = torch.zeros(int(log_rows), 3, dtype=torch.float64, device=dev) if log_rows > 0 else None
-        self._m = _abi.BeA2CTensors(*(self.exp_avg[k].data_ptr() for k in _PARAMS))
-        self._v = _abi.BeA2CTensors(*(self.exp_avg_sq[k].data_ptr() for k in _PARAMS))
-        self._keep = None
+        H, A, F = hip_policy.hidden, hip_policy.num_actions, hip_policy.env.obs_dim
+        super().__init__(hip_policy, policy, _abi.lib().be_a2c_adam, _PARAMS,
+                         ((H, F), (H,), (A, H), (A,), (1, H), (1,)), "adam", lr, betas, eps, log_rows)
 
-    def _check(self, what: str, k: str, x) -> torch.Tensor:
-        if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or not x.is_contiguous() or \
-                x.device != self.env.device or tuple(x.shape) != self._shapes[k]:
-            raise ValueError(f"{what} {k} must be a contiguous f32 tensor of shape {self._shapes[k]} on the "
-                             "HipPolicy's device")
-        return x
 
-    def _params(self):
-        ps = dict(self.policy.named_parameters())
-        if set(ps) != set(_PARAMS):
-            raise ValueError("HipAdam needs a Policy module (fc1, action_head, value_head)")
-        return [self._check("policy parameter", k, ps[k].detach()) for k in _PARAMS]
+def capture_graph(fn, dev, stream: Optional[torch.cuda.Stream] = None) -> torch.cuda.CUDAGraph:
+    """One call of ``fn`` recorded into one HIP graph: synchronise, capture on ``stream`` (default a new
+    one from torch's pool), synchronise."""
+    torch.cuda.synchronize(dev)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=torch.cuda.Stream(dev) if stream is None else stream):
+        fn()
+    torch.cuda.synchronize(dev)
+    return g
 
-    def step(self, grads=None, losses: Optional[torch.Tensor] = None) -> None:
-        """One Adam step and the re-pack, asynchronous on the caller's current stream.
-        grads: ``A2CGrad.grads`` (a dict keyed like ``policy.state_dict()``), default: the parameters'
-        ``.grad``.  losses: the 3 f64 of ``A2CGrad`` on the device, logged if there is a ``loss_log``."""
-        ws = self._params()
-        if grads is None:
-            ps = dict(self.policy.named_parameters())
-            if any(ps[k].grad is None for k in _PARAMS):
-                raise ValueError("HipAdam.step() without grads= needs every parameter's .grad")
-            gs = [self._check("gradient of", k, ps[k].grad) for k in _PARAMS]
-        else:
-            gs = [self._check("gradient of", k, grads[k]) for k in _PARAMS]
-        lp = gp = None
-        if losses is not None and self.loss_log is not None:
-            if losses.dtype != torch.float64 or losses.numel() != 3 or not losses.is_contiguous() or \
-                    losses.device != self.env.device:
-                raise ValueError("losses must be 3 contiguous f64 on the HipPolicy's device")
-            lp, gp = losses.data_ptr(), self.loss_log.data_ptr()
-        w = _abi.BeA2CTensors(*(x.data_ptr() for x in ws))
-        g = _abi.BeA2CTensors(*(x.data_ptr() for x in gs))
-        rc = self._lib.be_a2c_adam(self.hp._h, C.byref(w), C.byref(g), C.byref(self._m), C.byref(self._v),
-                                   self.state.data_ptr(), self.betas[0], self.betas[1], self.eps, lp, gp,
-                                   0 if gp is None else self.loss_log.shape[0], self.env._stream())
-        if rc:
-            _abi.check(rc, self.env._ctx)
-        self._keep = (ws, gs, losses)       # alive until the kernels have run
 
-    def zero_grad(self, set_to_none: bool = True) -> None:
-        self.policy.zero_grad(set_to_none=set_to_none)
+def capture_steps(step, T: int, chunk: int, dev, stream: Optional[torch.cuda.Stream] = None) -> list:
+    """``step(t, stream_ptr)`` for t = 0 .. T - 1 recorded into HIP graphs of ``chunk`` steps each, all on
+    one stream: what ``Rollout.capture`` and ``BlockRollout.capture`` keep in ``_graphs``."""
+    cap = torch.cuda.Stream(dev) if stream is None else stream
+    chunk = max(1, int(chunk))
 
-    @property
-    def lr(self) -> float:
-        return self._lr
-
-    @lr.setter
-    def lr(self, value: float) -> None:
-        self._lr = float(value)
-        self.state[3:].fill_(self._lr)      # stream-ordered: steps enqueued earlier keep the old rate
-
-    def step_count(self) -> int:
-        """Steps taken so far (synchronises)."""
-        return int(self.state[0].item())
-
-    def state_dict(self) -> dict:
-        """``torch.optim.Adam.state_dict()``'s format, parameters in ``policy.parameters()`` order, so
-        ``torch.optim.Adam(policy.parameters()).load_state_dict(...)`` continues this run (synchronises)."""
-        t = self.step_count()
-        groups = torch.optim.Adam(self.policy.parameters(), lr=self._lr, betas=self.betas,
-                                  eps=self.eps).state_dict()["param_groups"]
-        state = {}
-        if t > 0:
-            state = {i: {"step": torch.tensor(float(t)), "exp_avg": self.exp_avg[k].clone(),
-                         "exp_avg_sq": self.exp_avg_sq[k].clone()} for i, k in enumerate(_PARAMS)}
-        return {"state": state, "param_groups": groups}
-
-    def load_state_dict(self, sd: dict) -> None:
-        """From ``state_dict()`` of a HipAdam or of a ``torch.optim.Adam`` over ``policy.parameters()``.
-        beta^t is rebuilt by the repeated f64 product the device runs, so a HipAdam round trip
-        continues bit for bit."""
-        if len(sd["param_groups"]) != 1 or len(sd["param_groups"][0]["params"]) != len(_PARAMS):
-            raise ValueError("HipAdam needs one parameter group over the six Policy parameters")
-        grp = sd["param_groups"][0]
-        if grp.get("weight_decay", 0) != 0 or grp.get("amsgrad", False) or grp.get("maximize", False):
-            raise ValueError("HipAdam has no weight_decay, amsgrad or maximize")
-        st = sd["state"]
-        steps = {int(float(st[i]["step"])) for i in st}
-        if st and (len(st) != len(_PARAMS) or len(steps) != 1):
-            raise ValueError("HipAdam needs the state of all six parameters at one common step")
-        t = steps.pop() if st else 0
-        for k in _PARAMS:
-            i = grp["params"][_PARAMS.index(k)]
-            for mine, key in ((self.exp_avg, "exp_avg"), (self.exp_avg_sq, "exp_avg_sq")):
-                if st:
-                    if tuple(st[i][key].shape) != self._shapes[k]:
-                        raise ValueError(f"{key} of {k} has the wrong shape")
-                    mine[k].copy_(st[i][key])
-                else:
-                    mine[k].zero_()
-        self.betas, self.eps, self._lr = (float(grp["betas"][0]), float(grp["betas"][1])), float(grp["eps"]), \
-            float(grp["lr"])
-        p1, p2 = _beta_powers(t, self.betas)
-        self.state.copy_(torch.tensor([float(t), p1, p2, self._lr], dtype=torch.float64))
+    def steps(c0):
+        sp = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        for t in range(c0, min(T, c0 + chunk)):
+            step(t, sp)
+    return [capture_graph(lambda: steps(c0), dev, cap) for c0 in range(0, T, chunk)]
 
 
 class Rollout:
@@ -422,16 +330,7 @@ class Rollout:
             with torch.no_grad():
                 self.policy(self.env.obs[:64].float())
             torch.cuda.synchronize(dev)
-        cap = torch.cuda.Stream(dev) if stream is None else stream
-        self._graphs = []
-        for c0 in range(0, self.T, chunk):
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=cap):
-                sp = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-                for t in range(c0, min(self.T, c0 + chunk)):
-                    self.step(t, sp)
-            self._graphs.append(g)
-        torch.cuda.synchronize(dev)
+        self._graphs = capture_steps(self.step, self.T, chunk, dev, stream)
 
     def run(self) -> None:
         """Replay the captured horizon (capture() first)."""
@@ -590,77 +489,103 @@ def a2c_update(rollout: "Rollout", optimizer, gamma: float = 0.99, targets: str 
     return float(loss.detach())
 
 
-class A2CTrainer:
-    """The A2C training loop with no host round trip between two rollouts: per iteration
-    rollout -> ``a2c_targets_into`` -> ``A2CGrad`` -> ``HipAdam.step`` (which re-packs the policy), all
-    enqueued on the caller's current stream with nothing allocated and no synchronise.
+class GraphLoop:
+    """The loop of the three trainers: ``train(n)`` enqueues n passes on the caller's current stream without
+    a synchronise -- per pass ``_rollout()`` (nothing here), then ``_pass()``, or the one HIP graph ``capture()``
+    recorded of it.  A subclass sets ``env``, ``opt`` (the optimiser whose loss log ``losses()`` reads) and
+    ``_closes`` (what ``close()`` closes) and defines ``_pass``."""
 
-    Owns a ``Rollout(record_obs=True)`` (``backend="fused"``: ``be_policy_rollout`` launches;
-    ``"hip"``: the policy and step kernels, graph-replayed after ``capture()``), preallocated
-    ``A2CTargets``, an ``A2CGrad`` and a ``HipAdam`` (``.opt``; ``log_rows`` sizes its loss log).
-    ``capture()`` records the update half (targets, gradients, Adam + re-pack, loss log) into one HIP
-    graph, a linear chain on one stream, which ``train()`` then replays after each rollout."""
+    _graph = None
 
-    def __init__(self, env, policy: Policy, horizon: int, gamma: float = 0.99, backend: str = "fused",
-                 lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, seed: int = 0x5E1EC7, log_rows: int = 0,
-                 chunk: int = 100):
+    def _rollout(self) -> None:
+        pass
+
+    def capture(self, stream: Optional[torch.cuda.Stream] = None) -> None:
+        """Record one pass into one HIP graph, a linear chain.  stream: the stream to capture on; default
+        a new one from torch's pool."""
+        self._graph = capture_graph(self._pass, self.env.device, stream)
+
+    def train(self, iterations: int) -> None:
+        """``iterations`` passes, enqueued without a synchronise."""
+        for _ in range(int(iterations)):
+            self._rollout()
+            if self._graph is not None:
+                self._graph.replay()
+            else:
+                self._pass()
+
+    def losses(self) -> torch.Tensor:
+        """The optimiser's loss log on the host, one row per step in step order (synchronises)."""
+        return self.opt.losses()
+
+    def close(self) -> None:
+        self._graph = None
+        self._closes.close()
+
+
+class RolloutTrainer(GraphLoop):
+    """What ``A2CTrainer`` and ``BlockTrainer`` share: per iteration the rollout (replayed if it was captured),
+    then ``update()``: ``a2c_targets_into`` (no values) into the preallocated ``.targets``, the gradients
+    (``_grads``: the subclass's one call of ``.grad``; returns its grads and device losses) and ``opt.step``,
+    which re-packs the policy.  A subclass makes ``.grad`` and ``.opt`` once this ``__init__`` has run."""
+
+    GRAPH_CHUNK = 250               # rollout steps per captured graph
+
+    def __init__(self, env, policy, rollout, gamma: float):
         import numpy as np
-        if backend not in ("fused", "hip"):
-            raise ValueError("backend must be 'fused' or 'hip'")
         self.env, self.policy, self.gamma = env, policy, float(gamma)
-        self.rollout = Rollout(env, policy, horizon, backend=backend, record_obs=True, seed=seed, chunk=chunk)
-        T, N, dev = self.rollout.T, env.num_envs, env.device
+        self.rollout = self._closes = rollout
+        T, N, dev = rollout.T, env.num_envs, env.device
         self.targets = A2CTargets(torch.zeros(T, N, dtype=torch.float32, device=dev), None,
                                   torch.zeros(T, N, dtype=torch.uint8, device=dev), None)
-        self.grad = A2CGrad(env, policy)
-        self.opt = HipAdam(self.rollout.hp, policy, lr=lr, betas=betas, eps=eps, log_rows=log_rows)
         self._eps = float(np.finfo(np.float32).eps)
-        self._graph = None
 
     def update(self) -> None:
         """The update half on the recorded rollout: targets, gradients, Adam step + re-pack."""
         ro = self.rollout
         a2c_targets_into(self.env, ro.rewards, ro.dones, None, self.gamma, self._eps, None, self.targets)
-        g = self.grad(ro.obs[:-1], ro.actions, self.targets.returns_norm, self.targets.valid)
-        self.opt.step(g, self.grad._losses)
+        self.opt.step(*self._grads(ro, self.targets))
+
+    _pass = update
+
+    def _rollout(self) -> None:
+        ro = self.rollout
+        if ro._graphs:
+            ro.run()
+        else:
+            ro.run_eager()
 
     def capture(self, stream: Optional[torch.cuda.Stream] = None) -> None:
-        """Record ``update()`` into one HIP graph (and, for backend="hip", the rollout into its own:
-        ``Rollout.capture``).  stream: the stream to capture on; default a new one from torch's pool."""
-        dev = self.env.device
-        cap = torch.cuda.Stream(dev) if stream is None else stream
-        if self.rollout.backend == "hip":
-            self.rollout.capture(stream=cap)
-        torch.cuda.synchronize(dev)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, stream=cap):
-            self.update()
-        torch.cuda.synchronize(dev)
-        self._graph = g
+        """Record the rollout (its own ``capture``, ``GRAPH_CHUNK`` steps per graph) and ``update()`` (one
+        graph) into HIP graphs, linear chains on one stream, which ``train()`` then replays.  stream: the
+        stream to capture on; default a new one from torch's pool."""
+        cap = torch.cuda.Stream(self.env.device) if stream is None else stream
+        self.rollout.capture(chunk=self.GRAPH_CHUNK, stream=cap)
+        super().capture(cap)
 
-    def train(self, iterations: int) -> None:
-        """``iterations`` times rollout + update, enqueued without a synchronise."""
-        ro = self.rollout
-        for _ in range(int(iterations)):
-            if ro.backend == "hip" and not ro._graphs:
-                ro.run_eager()
-            else:
-                ro.run()
-            if self._graph is not None:
-                self._graph.replay()
-            else:
-                self.update()
 
-    def losses(self) -> torch.Tensor:
-        """The loss log as (iterations, 3) f64 on the host -- policy loss, value loss, active rows of
-        each iteration, the last ``log_rows`` of them once the ring has wrapped (synchronises)."""
-        log = self.opt.loss_log
-        if log is None:
-            raise ValueError("A2CTrainer(log_rows=...) keeps the loss log")
-        t, rows = self.opt.step_count(), log.shape[0]
-        out = log[:t] if t <= rows else torch.roll(log, -(t % rows), 0)
-        return out.cpu()
+class A2CTrainer(RolloutTrainer):
+    """The A2C training loop with no host round trip between two rollouts: per iteration
+    rollout -> ``a2c_targets_into`` -> ``A2CGrad`` -> ``HipAdam.step`` (which re-packs the policy), all
+    enqueued on the caller's current stream with nothing allocated and no synchronise.
 
-    def close(self) -> None:
-        self._graph = None
-        self.rollout.close()
+    Owns a ``Rollout(record_obs=True)`` (``backend="fused"``: ``be_policy_rollout`` launches, nothing to
+    capture; ``"hip"``: the policy and step kernels, graph-replayed after ``capture()``), preallocated
+    ``A2CTargets``, an ``A2CGrad`` and a ``HipAdam`` (``.opt``; ``log_rows`` sizes its loss log).
+    ``capture()`` records the update half (targets, gradients, Adam + re-pack, loss log) into one HIP
+    graph, a linear chain on one stream, which ``train()`` then replays after each rollout.
+    ``losses()``: the loss log as (iterations, 3) f64 on the host -- policy loss, value loss, active rows of
+    each iteration, the last ``log_rows`` of them once the ring has wrapped (synchronises)."""
+
+    def __init__(self, env, policy: Policy, horizon: int, gamma: float = 0.99, backend: str = "fused",
+                 lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, seed: int = 0x5E1EC7, log_rows: int = 0,
+                 chunk: int = 100):
+        if backend not in ("fused", "hip"):
+            raise ValueError("backend must be 'fused' or 'hip'")
+        super().__init__(env, policy, Rollout(env, policy, horizon, backend=backend, record_obs=True, seed=seed,
+                                              chunk=chunk), gamma)
+        self.grad = A2CGrad(env, policy)
+        self.opt = HipAdam(self.rollout.hp, policy, lr=lr, betas=betas, eps=eps, log_rows=log_rows)
+
+    def _grads(self, ro, tg):
+        return self.grad(ro.obs[:-1], ro.actions, tg.returns_norm, tg.valid), self.grad._losses

@@ -183,7 +183,54 @@ static void test_out_at() {
   }
 }
 
+// be_a2c_adam's and be_mlp_opt's shared argument check: each rejection, in the order of the checks
+// (every case is valid up to the argument it names, so the message shows which check fired).
+static void test_optim_args() {
+  alignas(8) static double buf[8];             // only addresses: nothing is read through them
+  const double* state = buf;
+  const double* losses = buf + 4;
+  const double* log = buf + 6;
+  const double* const off4[3] = {(const double*)((const char*)state + 4), (const double*)((const char*)losses + 4),
+                                 (const double*)((const char*)log + 4)};
+  const double nan = strtod("nan", nullptr);
+  const auto has = [](const char* msg, const char* part) { return msg && strstr(msg, part); };
+  // a fully valid call, with and without a log (log_rows is not looked at without one)
+  CHECK(optim_args_error(state, true, 0.9, 0.999, 1e-8, losses, log, 2) == nullptr);
+  CHECK(optim_args_error(state, true, 0.0, 0.0, 0.0, nullptr, nullptr, 0) == nullptr);
+  CHECK(optim_args_error(state, true, 0.9, 0.999, 1e-8, nullptr, nullptr, -3) == nullptr);
+  // the state: NULL, and 4 bytes past an 8-byte boundary (ahead of every other complaint)
+  CHECK(has(optim_args_error(nullptr, true, 0.9, 0.999, 1e-8, losses, log, 2), "state"));
+  CHECK(has(optim_args_error(off4[0], true, 0.9, 0.999, 1e-8, losses, log, 2), "state"));
+  CHECK(has(optim_args_error(nullptr, true, 1.0, -0.1, -1.0, losses, nullptr, 0), "state"));
+  // the Adam constants, beta1 before beta2 before eps; a NaN is out of every range
+  CHECK(has(optim_args_error(state, true, 1.0, 0.999, 1e-8, losses, log, 2), "beta1"));
+  CHECK(has(optim_args_error(state, true, 1.0, -0.1, -1.0, losses, log, 2), "beta1"));
+  CHECK(has(optim_args_error(state, true, 0.9, -0.1, 1e-8, losses, log, 2), "beta2"));
+  CHECK(has(optim_args_error(state, true, 0.9, -0.1, -1.0, losses, log, 2), "beta2"));
+  CHECK(has(optim_args_error(state, true, nan, 0.999, 1e-8, losses, log, 2), "beta1"));
+  CHECK(has(optim_args_error(state, true, 0.9, nan, 1e-8, losses, log, 2), "beta2"));
+  CHECK(has(optim_args_error(state, true, 0.9, 0.999, -1.0, losses, log, 2), "eps"));
+  CHECK(has(optim_args_error(state, true, 0.9, 0.999, nan, losses, log, 2), "eps"));
+  CHECK(has(optim_args_error(state, true, 0.9, 0.999, -1.0, losses, nullptr, 0), "eps"));   // ahead of the log's checks
+  // the loss log: losses without a log and the reverse, each of the two misaligned by 4, no rows
+  CHECK(has(optim_args_error(state, true, 0.9, 0.999, 1e-8, losses, nullptr, 0), "losses and loss_log"));
+  CHECK(has(optim_args_error(state, true, 0.9, 0.999, 1e-8, nullptr, log, 2), "losses and loss_log"));
+  CHECK(has(optim_args_error(state, true, 0.9, 0.999, 1e-8, off4[1], log, 2), "not 8-byte aligned"));
+  CHECK(has(optim_args_error(state, true, 0.9, 0.999, 1e-8, losses, off4[2], 2), "not 8-byte aligned"));
+  CHECK(has(optim_args_error(state, true, 0.9, 0.999, 1e-8, off4[1], off4[2], 0), "not 8-byte aligned"));   // ahead of log_rows
+  CHECK(has(optim_args_error(state, true, 0.9, 0.999, 1e-8, losses, log, 0), "log_rows"));
+  CHECK(has(optim_args_error(state, true, 0.9, 0.999, 1e-8, losses, log, -1), "log_rows"));
+  // plain SGD: the betas and eps are not looked at, the state and the log are
+  CHECK(optim_args_error(state, false, 1.0, -0.1, -1.0, losses, log, 2) == nullptr);
+  CHECK(optim_args_error(state, false, nan, nan, nan, nullptr, nullptr, 0) == nullptr);
+  CHECK(has(optim_args_error(off4[0], false, 0.9, 0.999, 1e-8, losses, log, 2), "state"));
+  CHECK(has(optim_args_error(state, false, 1.0, -0.1, -1.0, losses, nullptr, 0), "losses and loss_log"));
+  CHECK(has(optim_args_error(state, false, 1.0, -0.1, -1.0, losses, off4[2], 2), "not 8-byte aligned"));
+  CHECK(has(optim_args_error(state, false, 1.0, -0.1, -1.0, losses, log, 0), "log_rows"));
+}
+
 int main() {
+  test_optim_args();
   test_pool_book();
   test_blob();
   test_pool_entry();
