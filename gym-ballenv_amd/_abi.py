@@ -29,6 +29,7 @@ EXPORTS = ("be_abi_version", "be_config_default", "be_config_check", "be_step_by
            "be_pool_fill", "be_pool_invalidate", "be_pool_set_period", "be_pool_period", "be_pool_bytes", "be_pool_entry", "be_policy_create", "be_policy_destroy", "be_policy_load", "be_policy_act",
            "be_policy_rollout", "be_policy_bytes", "be_observe_blocks",
            "be_mlp_create", "be_mlp_destroy", "be_mlp_load", "be_mlp_act", "be_mlp_bytes",
+           "be_mlp_rollout", "be_mlp_rollout_kernel",
            "be_mlp_grad_workspace_bytes", "be_mlp_grad", "be_mlp_opt",
            "be_board_config_default", "be_board_create", "be_board_destroy", "be_board_last_error",
            "be_board_reset", "be_board_step", "be_board_rollout", "be_board_observe", "be_board_status",
@@ -197,6 +198,8 @@ def lib() -> C.CDLL:
         "be_mlp_destroy": (C.c_int, [vp]),
         "be_mlp_load": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp]),
         "be_mlp_act": (C.c_int, [vp, P(BeState), vp, vp, P(BeActOut), u64, vp]),
+        "be_mlp_rollout": (C.c_int, [vp, P(BeState), vp, vp, i32, P(BeOut), P(BeActOut), u64, vp]),
+        "be_mlp_rollout_kernel": (C.c_char_p, [vp]),
         "be_mlp_bytes": (i64, [vp]),
         "be_mlp_grad_workspace_bytes": (i64, [vp, i32, i32, i32, i32]),
         "be_mlp_grad": (C.c_int, [vp, vp, vp, vp, vp, i64, i32, C.c_double, P(BeMlpWeights), vp, i64, P(BeMlpGrads),

@@ -13,7 +13,8 @@ Reference:
 ``HipBlockPolicy`` runs that select_action for every env of a ``BatchedBallEnv`` in one launch of the
 kernel in csrc/mlp_policy.hip (``be_mlp_act``), which computes ``prep_state2`` of each env's state
 itself: the 29-byte row makes no round trip.  ``BlockRollout`` is the T-step loop of
-``be_mlp_act`` + ``be_step`` writing straight into (T, N) buffers, capturable into HIP graphs;
+``be_mlp_act`` + ``be_step`` writing straight into (T, N) buffers, capturable into HIP graphs, or with
+backend="fused" the same steps as ``be_mlp_rollout`` launches (policy and env step in one kernel, DESIGN §3.17);
 ``reinforce_losses`` / ``reinforce_update`` are the batched ``finish_episode`` over such a record
 (targets from ``be_a2c_targets``; gradients from torch autograd over the recorded rows, or with
 grads="hip" from ``BlockGrad``: ``be_mlp_grad``, csrc/mlp_grad.hip, straight from the u8 rows).
@@ -161,6 +162,13 @@ class HipBlockPolicy:
     def packed_bytes(self) -> int:
         return int(self._lib.be_mlp_bytes(self._h))
 
+    @property
+    def rollout_kernel(self) -> Optional[str]:
+        """The fused kernel instance ``be_mlp_rollout`` launches for this env and network
+        (``be_mlp_rollout_kernel``), or None where it loops ``be_mlp_act`` + ``be_step``."""
+        r = self._lib.be_mlp_rollout_kernel(self._h)
+        return r.decode() if r else None
+
     def _check_rows(self, x: torch.Tensor, name: str) -> None:
         if x.dtype != torch.uint8 or tuple(x.shape) != (self.env.num_envs, BLOCKS) or not x.is_contiguous() or \
                 x.device != self.env.device:
@@ -201,10 +209,19 @@ class BlockRollout:
     the block counts the action was drawn from into row t of ``blocks`` (T, N, 29) u8), then ``be_step``
     writes rewards and dones into row t.  The per-step out-structs point into the (T, N) buffers, so
     there are no copy kernels; ``capture()`` records the loop into HIP graphs (a linear chain on one
-    stream) and ``run()`` replays them."""
+    stream) and ``run()`` replays them.
 
-    def __init__(self, env, policy: BlockPolicy, horizon: int, record_obs: bool = False, seed: int = 0x5E1EC7):
+    ``backend="fused"`` runs the same T steps as ``be_mlp_rollout`` launches of ``chunk`` steps each into the
+    same buffers: the policy and the env step in one kernel, each env's state in registers and the packed
+    weights in LDS (csrc/ballenv.hip's ``mlp_rollout_kernel``; bit-identical to ``"hip"``).  There is then
+    nothing to capture: ``run()`` and ``run_eager()`` both issue the launches, and ``step(t)`` raises."""
+
+    def __init__(self, env, policy: BlockPolicy, horizon: int, record_obs: bool = False, seed: int = 0x5E1EC7,
+                 backend: str = "hip", chunk: int = 100):
+        if backend not in ("hip", "fused"):
+            raise ValueError("backend must be 'hip' or 'fused'")
         self.env, self.policy, self.T, self.seed = env, policy, int(horizon), int(seed)
+        self.backend, self.chunk = backend, max(1, int(chunk))
         dev, N, T = env.device, env.num_envs, self.T
         self.actions = torch.zeros(T, N, dtype=torch.uint8, device=dev)
         self.log_probs = torch.zeros(T, N, dtype=torch.float32, device=dev)
@@ -221,8 +238,25 @@ class BlockRollout:
                                       o.truncated, o.terminal_obs, o.final_return, o.final_len, o.stats)
                            for t in range(T)]
 
+    def run_fused(self, stream_ptr=None) -> None:
+        """The horizon as be_mlp_rollout launches of ``chunk`` steps (backend="fused")."""
+        env, lib = self.env, self._lib
+        s = env._stream() if stream_ptr is None else stream_ptr
+        for c0 in range(0, self.T, self.chunk):
+            k = min(self.chunk, self.T - c0)
+            out = _abi.BeOut(None, None, self.rewards[c0].data_ptr(), self.dones[c0].data_ptr(), None, None,
+                             None, None, env._out.stats)
+            act = _abi.BeActOut(self.actions[c0].data_ptr(), self.log_probs[c0].data_ptr(), None, None)
+            rec = None if self.blocks is None else self.blocks[c0].data_ptr()
+            rc = lib.be_mlp_rollout(self.hp._h, C.byref(env._st), env.obs.data_ptr(), rec, k, C.byref(out),
+                                    C.byref(act), self.seed & (2**64 - 1), s)
+            if rc:
+                _abi.check(rc, env._ctx)
+
     def step(self, t: int, stream_ptr=None) -> None:
         """select_action + env step of every env, results into row t."""
+        if self.backend == "fused":
+            raise RuntimeError("backend='fused' has no single step: run() / run_eager() issue be_mlp_rollout launches")
         env, lib = self.env, self._lib
         s = env._stream() if stream_ptr is None else stream_ptr
         rec = None if self.blocks is None else self.blocks[t].data_ptr()
@@ -236,16 +270,23 @@ class BlockRollout:
             _abi.check(rc, env._ctx)
 
     def run_eager(self) -> None:
+        if self.backend == "fused":
+            return self.run_fused()
         for t in range(self.T):
             self.step(t)
 
     def capture(self, chunk: int = 250, stream: Optional[torch.cuda.Stream] = None) -> None:
         """Record the T steps into HIP graphs of ``chunk`` steps each (stream: the stream to capture
         on; default a new one from torch's pool)."""
+        if self.backend == "fused":     # a few launches per horizon: nothing to capture
+            self._graphs = []
+            return
         self._graphs = capture_steps(self.step, self.T, chunk, self.env.device, stream)
 
     def run(self) -> None:
         """Replay the captured horizon (capture() first)."""
+        if self.backend == "fused":
+            return self.run_fused()
         if not self._graphs:
             raise RuntimeError("capture() first")
         for g in self._graphs:
@@ -541,13 +582,16 @@ class BlockTrainer(RolloutTrainer):
     Owns a ``BlockRollout(record_obs=True)``, preallocated ``A2CTargets`` (returns_norm and valid), a
     ``BlockGrad`` and a ``HipBlockOptim`` (``.opt``; ``log_rows`` sizes its loss log).  ``capture()`` records
     the rollout (``BlockRollout.capture``, ``chunk`` steps per graph) and the update half into HIP graphs,
-    linear chains on one stream, which ``train()`` then replays.
+    linear chains on one stream, which ``train()`` then replays.  ``backend="fused"``: the rollout half is
+    ``be_mlp_rollout`` launches of ``chunk`` steps (nothing of it to capture), the update half still one graph.
     ``losses()``: the loss log as (iterations, 2) f64 on the host -- the REINFORCE loss and the active rows
     of each iteration, the last ``log_rows`` of them once the ring has wrapped (synchronises)."""
 
     def __init__(self, env, policy: BlockPolicy, horizon: int, gamma: float = 0.99, lr: float = 1e-2,
-                 betas=(0.9, 0.999), eps: float = 1e-8, seed: int = 0x5E1EC7, log_rows: int = 0, chunk: int = 250):
-        super().__init__(env, policy, BlockRollout(env, policy, horizon, record_obs=True, seed=seed), gamma)
+                 betas=(0.9, 0.999), eps: float = 1e-8, seed: int = 0x5E1EC7, log_rows: int = 0, chunk: int = 250,
+                 backend: str = "hip"):
+        super().__init__(env, policy, BlockRollout(env, policy, horizon, record_obs=True, seed=seed, backend=backend,
+                                                   chunk=chunk), gamma)
         self.chunk = self.GRAPH_CHUNK = int(chunk)
         self.grad = BlockGrad(env, policy)
         self.opt = HipBlockOptim(self.rollout.hp, policy, "adam", lr=lr, betas=betas, eps=eps, log_rows=log_rows)

@@ -27,6 +27,10 @@ object) and linked into one shared library:
                     from the env state; shares blocks_core.h (prep_state2 of one env) with features.hip;
                     and next to its pack kernel the Adam / SGD step fused with the re-pack (be_mlp_opt,
                     optim_core.h)
+  csrc/mlp_core.h   the block MLP's packed image and forward, shared by mlp_policy.hip (be_mlp_act) and ballenv.hip's
+                    fused block-policy rollout (mlp_rollout_kernel behind be_mlp_rollout); ballenv.hip's
+                    VGPR_MFMA holds for it as for the fused policy rollouts: its accumulators are read by VALU code
+                    (relu, the logits) right after each layer
   csrc/mlp_grad.hip the block-count MLP's REINFORCE / cross-entropy losses and gradients of recorded rows
                     (f32 MFMAs; no VGPR_MFMA, for a2c_grad.hip's reason: the gradient accumulators live
                     for the whole kernel, the AGPR half of the register file is where they belong)
@@ -57,7 +61,7 @@ KARG_PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
 UNITS = {"ballenv.hip": [*VGPR_MFMA, *KARG_PRELOAD], "abi.hip": [], "policy.hip": ["-fno-slp-vectorize", *VGPR_MFMA],
          "features.hip": [], "board.hip": [], "a2c.hip": [], "a2c_grad.hip": [], "a2c_adam.hip": [],
          "mlp_policy.hip": [], "mlp_grad.hip": []}
-HEADERS = [HDR, *(os.path.join(CSRC, h) for h in ("philox.h", "internal.h", "host_logic.h", "pool_layout.h", "policy_core.h", "blocks_core.h", "diag.h",
+HEADERS = [HDR, *(os.path.join(CSRC, h) for h in ("philox.h", "internal.h", "host_logic.h", "pool_layout.h", "policy_core.h", "blocks_core.h", "mlp_core.h", "diag.h",
                                               "step_types.h", "optim_core.h"))]
 
 

@@ -44,7 +44,8 @@ struct be_ctx {
   int64_t pool_bytes;
   Launch pool_fill;    // the pool's fill kernel for this window
   PoolBook book;       // the pool's owner state, and when be_step queues a fill
-  mutable struct { KFn fn; int lds; bool ok; } lds_cache[4];   // fits_lds() answers per (kernel, dynamic LDS)
+  mutable struct { const void* fn; int lds; bool ok; } lds_cache[16];  // fits_lds() answers per (kernel, dynamic LDS): the two rollouts and the block-policy
+                                                                        // rollout's instances (up to 4 under forced-waves A/B runs); full: asked again per call
   mutable std::mutex lds_mu;                                    // guards lds_cache (const entries may race)
   char err[512];
 };
@@ -54,15 +55,15 @@ struct be_ctx {
 // table) and the config-5 kernel is within 72 B of the CU's 160 KB at the default R = 25, so a
 // larger R must take the per-step fallback instead of failing the launch.
 static bool fits_lds(const be_ctx* ctx, const Launch& L) {
-  if (!L.fn) return false;
+  if (!L.fn && !L.fnm) return false;
+  const void* fn = L.entry();
   std::lock_guard<std::mutex> lock(ctx->lds_mu);
   for (auto& c : ctx->lds_cache)
-    if (c.fn == L.fn && c.lds == L.lds) return c.ok;
+    if (c.fn == fn && c.lds == L.lds) return c.ok;
   hipFuncAttributes fa;
-  bool ok = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(L.fn)) == hipSuccess &&
-            (int64_t)fa.sharedSizeBytes + L.lds <= (int64_t)ctx->max_lds;
+  bool ok = hipFuncGetAttributes(&fa, fn) == hipSuccess && (int64_t)fa.sharedSizeBytes + L.lds <= (int64_t)ctx->max_lds;
   for (auto& c : ctx->lds_cache)
-    if (!c.fn) { c.fn = L.fn; c.lds = L.lds; c.ok = ok; break; }
+    if (!c.fn) { c.fn = fn; c.lds = L.lds; c.ok = ok; break; }
   return ok;
 }
 
@@ -528,6 +529,31 @@ int be_internal_policy_rollout(be_ctx* ctx, const be_state* st, const be_pol_rol
   launch_kernel(L, a, (hipStream_t)stream);
   const int rc = be_launched(ctx->err);
   return rc ? rc : 1;
+}
+
+int be_internal_mlp_rollout(be_ctx* ctx, const be_state* st, const be_mlp_rollout_args* r, void* stream) {
+  const Launch L = pick_mlp_rollout(ctx->cfg, fixed_ok(ctx), r->layers, r->waves);
+  if (!fits_lds(ctx, L)) return 0;   // the caller loops be_mlp_act + be_step instead
+  KParams a = make_params(ctx, st, r->out);
+  a.steps = r->steps;
+  const MlpRollParams q{r->img, r->blocks_out, r->act->action, r->act->log_prob, r->seed, r->num_actions, r->final_relu};
+  launch_mlp_rollout(L, a, q, (hipStream_t)stream);
+  if (int rc = be_launched(ctx->err)) return rc;
+  // the window obs of the final state, as the loop's last be_step leaves it: what be_observe writes
+  const be_out last{r->obs_last, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  KParams o = make_params(ctx, st, &last);
+  obs_only(o);
+  const int rc = launch(ctx, MODE_OBSERVE, o, stream);
+  return rc ? rc : 1;
+}
+
+const char* be_internal_mlp_rollout_name(be_ctx* ctx, int32_t layers, int32_t waves) {
+  static thread_local char name[48];
+  const Launch L = pick_mlp_rollout(ctx->cfg, fixed_ok(ctx), layers, waves);
+  const DeviceGuard dg(ctx->device);   // fits_lds queries the context's device
+  if (dg.err != hipSuccess || !fits_lds(ctx, L)) return nullptr;
+  memcpy(name, L.name, sizeof name);
+  return name;
 }
 
 extern "C" {

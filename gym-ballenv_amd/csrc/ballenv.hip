@@ -50,6 +50,7 @@
 #include <stdio.h>
 
 #include "ballenv.h"
+#include "mlp_core.h"
 #include "philox.h"
 #include "policy_core.h"
 #include "step_types.h"
@@ -87,8 +88,7 @@ __device__ __forceinline__ double u2d(uint32_t lo, uint32_t hi) {
 #include "diag.h"
 
 // ------------------------------------------------------------------ helpers
-__device__ __forceinline__ int px(int32_t p) { return (int)(int16_t)(p & 0xFFFF); }
-__device__ __forceinline__ int py(int32_t p) { return p >> 16; }
+// (px / py, a packed position's x and y: blocks_core.h)
 __device__ __forceinline__ int32_t pk(int x, int y) {
   return (int32_t)(((uint32_t)x & 0xFFFFu) | ((uint32_t)y << 16));
 }
@@ -3413,6 +3413,247 @@ __global__ __launch_bounds__(BLOCK_THREADS) void rollout_kernel(KParams p) {
   }
 }
 
+// ------------------------------------------------------------------ the fused block-policy rollout
+// mlp_rollout_kernel<LAYERS, NW> (be_mlp_rollout): p.steps steps of be_mlp_act + be_step in one
+// launch -- ball_env_reinforce.py's episode loop (:309-336: select_action :76-85 on prep_state2 :130-172,
+// then env.step) for every env, with the env state in registers and the packed block MLP (mlp_core.h) in LDS.
+//
+// A wave owns 32 envs: the granularity of a statistics slot, so the wave folds its own slot as
+// rollout_kernel's half-waves do.  Lane l < 32 holds env e0 + l and runs its physics; all 64 lanes run
+// the two 16-env tiles' MFMAs (lane (c, g) as in mlp_act_kernel: an MFMA column is an env, so an env's
+// logits are mlp_act_kernel's bits in either tile) and wave_resets.  Lanes 32..63 carry a copy of the
+// state of lanes 0..31 that nothing reads: they store nothing and take no part in a ballot.
+// Workgroups of NW waves share only the staged image and the tables, behind the kernel's one block
+// barrier; the step loop syncs within the wave alone, so a wave with no env just leaves.
+// No window observation is produced: the caller queues the observe kernel behind this one for obs_last.
+//
+// The dynamic LDS, the one source of the offsets and of the launch's byte count (words of 4 bytes):
+//   [the MlpLayout image][NW slices: 32 rows of counts at 8 words | 32 rows of logits at MLP_ZP |
+//                         wave_resets' scratch | a reset pass's new obstacles [slot][k]]
+constexpr int MLP_ROLL_WT = 5;   // wave_resets' window: its row masks are not used here, it only sizes the scratch
+template <int LAYERS, int NW>
+struct MlpRollLds {
+  static constexpr int IMG = mlp_layout(LAYERS, MLP_HT, MLP_HT).total;
+  static constexpr int P = 64 / (FIX_NS + FIX_ND + 1);                  // envs per reset pass
+  static constexpr int ROWS = 0;
+  static constexpr int Z = ROWS + 32 * 8;
+  static constexpr int RS = Z + 32 * MLP_ZP;
+  static constexpr int OST = RS + ((P * (Geo<MLP_ROLL_WT>::K + 8) + 3) & ~3);
+  static constexpr int SLICE = OST + 64;
+  static constexpr int bytes = (IMG + NW * SLICE) * 4;
+  static_assert(IMG % 4 == 0 && SLICE % 4 == 0 && Z % 4 == 0, "the slices stay 16-byte aligned");
+  static_assert(P * (FIX_NS + FIX_ND) <= 64, "a reset pass's obstacles fit their stash");
+};
+static_assert(MlpRollLds<3, 8>::bytes == 91264 + 8 * 3600 && MlpRollLds<2, 1>::bytes == 25216 + 3600,
+              "the block-policy rollouts' LDS");
+template <int LAYERS, int NW>
+__global__ __launch_bounds__(64 * NW) void mlp_rollout_kernel(KParams p, MlpRollParams q) {
+  using Lds = MlpRollLds<LAYERS, NW>;
+  constexpr int NSC = FIX_NS, NDC = FIX_ND, G = NSC + NDC, WT = MLP_ROLL_WT, KR = Geo<WT>::K;
+  constexpr MlpLayout L = mlp_layout(LAYERS, MLP_HT, MLP_HT);
+  constexpr int TW = (int)(sizeof(Tables) / 4);
+  extern __shared__ __align__(16) uint8_t mlp_smem[];
+  __shared__ Tables t;
+  const int N = p.n, tid = (int)threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int e0 = ((int)blockIdx.x * NW + w) * 32, i = e0 + (lane & 31);
+  const bool valid = lane < 32 && i < N;
+  const uint32_t ic = (uint32_t)min(i, N - 1), gid = (uint32_t)p.gid0 + (uint32_t)i;
+  const int l15 = lane & 15, l4 = lane >> 4;
+
+  // ---- state into registers (rollout_kernel's order)
+  uint32_t episode = ld_s(p.episode, ic);
+  int len = ld_s(p.ep_len, ic);
+  const int32_t agent0 = ld_s(p.agent, ic);
+  int32_t goal = ld_s(p.goal, ic);
+  int32_t dp[NDC], so[NSC];
+  int dgi[NDC];
+#pragma unroll
+  for (int j = 0; j < NDC; ++j) { dp[j] = ld_s(p.dyn_obs + (size_t)j * N, ic); dgi[j] = ld_s(p.dyn_goal + (size_t)j * N, ic); }
+#pragma unroll
+  for (int j = 0; j < NSC; ++j) so[j] = ld_s(p.static_obs + (size_t)j * N, ic);
+  double old_dist = ld_s(p.prev_dist, ic), total = ld_s(p.total_dist, ic), ret = ld_s(p.ep_return, ic);
+  // the wave's stats slot (be_stats_slots: one per 32 envs; none past N)
+  double* slot = (p.stats && e0 < N) ? p.stats + (size_t)(e0 >> 5) * 8 : nullptr;
+  WaveStats acc{0.0, 0.0, 0.0, 0.0, INFINITY, -INFINITY};
+  if (slot) acc = WaveStats{slot[0], slot[1], slot[2], slot[3], slot[4], slot[5]};
+  // ---- the tables and the packed image, once per launch, behind the only block barrier
+  for (int k = tid; k < TW; k += 64 * NW) reinterpret_cast<uint32_t*>(&t)[k] = reinterpret_cast<const uint32_t*>(p.tables)[k];
+  stage_image<64 * NW, 16>(reinterpret_cast<uint4*>(mlp_smem), reinterpret_cast<const uint4*>(q.img), L.total / 4, tid);
+  __syncthreads();
+  if (e0 >= N) return;   // (a partial last workgroup: no barrier follows)
+  const float* Wimg = reinterpret_cast<const float*>(mlp_smem);
+  uint32_t* slice = reinterpret_cast<uint32_t*>(mlp_smem) + L.total + w * Lds::SLICE;
+  uint32_t* rows = slice + Lds::ROWS;
+  float* Zs = reinterpret_cast<float*>(slice + Lds::Z);
+  uint32_t* wl = slice + Lds::RS;
+  int32_t* ost = reinterpret_cast<int32_t*>(slice + Lds::OST);
+  const int nrows = min(32, N - e0);          // this wave's envs
+  const int ntile = nrows > 16 ? 2 : 1;       // (wave-uniform)
+
+  int ax = px(agent0), ay = py(agent0);
+  uint32_t st_flags = 0;
+  bool was_reset = false;   // statics / goal / total / episode changed: store them at the end
+  const uint32_t R2 = (uint32_t)(p.R * p.R);
+
+  for (int s = 0; s < p.steps; ++s) {
+    const size_t so_n = (size_t)s * N;
+    // ---- 1: prep_state2 of this lane's env from its registers (blocks_core.h) into the slice
+    {
+      uint32_t w8[BLK_WORDS];
+      blocks_init(w8, pk(ax, ay), goal);
+#pragma unroll
+      for (int j = 0; j < NSC; ++j) blocks_add(w8, ax, ay, so[j], true);
+#pragma unroll
+      for (int j = 0; j < NDC; ++j) blocks_add(w8, ax, ay, dp[j], true);
+      if (lane < 32) {
+        uint4* r = reinterpret_cast<uint4*>(rows + lane * 8);
+        r[0] = make_uint4(w8[0], w8[1], w8[2], w8[3]);
+        r[1] = make_uint4(w8[4], w8[5], w8[6], w8[7]);
+      }
+    }
+    wave_sync();
+    if (q.blocks_out) {   // the wave's rows are one contiguous run of the output
+      const uint8_t* rb = reinterpret_cast<const uint8_t*>(rows);
+      uint8_t* dst = q.blocks_out + (so_n + (size_t)e0) * BLK_ROW;
+      const int nbytes = nrows * BLK_ROW;
+      for (int b = lane; b < nbytes; b += 64) {
+        const int r = b / BLK_ROW;
+        dst[b] = rb[r * 32 + (b - r * BLK_ROW)];
+      }
+    }
+    // ---- 2: the forward of the wave's tiles (mlp_core.h): x[k] = count 4 k + l4 of env 16 tt + l15
+#pragma unroll 1
+    for (int tt = 0; tt < ntile; ++tt) {
+      const uint4* row = reinterpret_cast<const uint4*>(rows + (16 * tt + l15) * 8);
+      const uint4 r0 = row[0], r1 = row[1];
+      const uint32_t wv[MLP_KS1] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
+      float x[MLP_KS1];
+#pragma unroll
+      for (int k = 0; k < MLP_KS1; ++k) x[k] = (float)((wv[k] >> (8 * l4)) & 0xFFu);
+      const f32x4 z = mlp_forward<LAYERS, MLP_HT, MLP_HT>(Wimg, x, lane);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) Zs[(16 * tt + l15) * MLP_ZP + 4 * l4 + r] = q.final_relu ? fmaxf(z[r], 0.0f) : z[r];
+    }
+    wave_sync();
+    // ---- 3: select_action's tail (ball_env_reinforce.py:76-85) on the env's own lane
+    int a;
+    {
+      float lp, val;
+      a = policy_finish<MLP_NO>(Zs + (lane & 31) * MLP_ZP, Wimg + L.hb, q.num_actions, gid, episode, (uint32_t)len,
+                                q.seed, nullptr, lp, val);
+      a = valid ? a : 0;   // (a lane with no env read no logits of its own)
+      if (valid) {
+        q.action[so_n + i] = (uint8_t)a;
+        if (q.log_prob) q.log_prob[so_n + i] = lp;
+      }
+    }
+    // ---- 4: the step, as rollout_kernel takes it (no near list, no raster, no obs row)
+    const int gx = px(goal), gy = py(goal);
+    int dx, dy;
+    unit_move(a, p.num_actions, p.amx, p.amy, dx, dy, st_flags);
+    ax = min(max(ax + dx, 0), p.screen_w);   // unit speeds (pick_mlp_rollout's precondition)
+    ay = min(max(ay + dy, 0), p.screen_h);
+    bool hs = false, hd = false;
+    const bool change = goal_counter(len, p.goal_change, p.inv_g1) >= p.goal_change;
+    const u4 b0 = philox(gid, episode, (uint32_t)len, tag(PURPOSE_STEP_OBS, 0u), p.seed);
+    const v2s agv = __builtin_bit_cast(v2s, pk(ax, ay));
+    auto obstacle_pk = [&](int32_t opk, bool& hit) {   // be_kernel's packed int16x2 test
+      const v2s d = __builtin_elementwise_sub_sat(__builtin_bit_cast(v2s, opk), agv);
+      hit |= (uint32_t)__builtin_amdgcn_sdot2(d, d, 0, false) <= R2;
+    };
+    static_assert(NDC <= 5, "one Philox block holds the dynamic obstacles' fields");
+#pragma unroll
+    for (int j = 0; j < NDC; ++j) {
+      int ox = px(dp[j]), oy = py(dp[j]);
+      dgi[j] = dyn_move_fixed(p, t, ox, oy, dgi[j], t.speed[j], change, pick_field(b0, j), st_flags);
+      dp[j] = pk(ox, oy);
+      obstacle_pk(dp[j], hd);
+    }
+#pragma unroll
+    for (int j = 0; j < NSC; ++j) obstacle_pk(so[j], hs);
+
+    // ---- distance, reward, done (ballenv_env.py:268-286, 200-229)
+    const double dist = calc_dist_lib(gx, gy, ax, ay);
+    double reward = 0.0 - p.time_penalty;
+    reward += (old_dist - dist) / total;
+    reward = collision_penalty(reward, hs, hd, p.static_penalty, p.dynamic_penalty);
+    ret += reward;
+    ++len;
+    const bool env_done = (dist < p.threshold_goal) || hs || hd;
+    const bool trunc = p.time_limit > 0 && len >= p.time_limit;
+    const bool done = env_done || trunc;
+    old_dist = dist;
+    if (valid) {
+      p.reward[so_n + i] = reward;
+      p.done[so_n + i] = (uint8_t)done;
+      if (p.truncated) p.truncated[so_n + i] = (uint8_t)(trunc && !env_done);
+      if (done) {
+        if (p.final_return) p.final_return[so_n + i] = ret;
+        if (p.final_len) p.final_len[so_n + i] = len;
+      }
+    }
+    // ---- 5: the step kernel's per-slot fold, step by step (same order: bit-identical sums)
+    if (p.stats) {
+      WaveStats lo, hi;
+      wave_stats2(done && valid, ret, len, lo, hi);
+      if (slot && lo.n > 0.0) {
+        acc.n += lo.n; acc.s1 += lo.s1; acc.s2 += lo.s2; acc.sl += lo.sl;
+        acc.mn = fmin(acc.mn, lo.mn); acc.mx = fmax(acc.mx, lo.mx);
+      }
+    }
+    // ---- 6: autoreset: the wave draws its finished envs' new state, picked up into the env's registers
+    const unsigned long long m = __ballot(valid && done && p.autoreset);
+    if (m) {
+      uint32_t xrows[KR];
+      int gxr = gx, gyr = gy, ncnt = 0;
+      auto osink = [&](int sl, int k, int, int32_t o) { ost[sl * G + k] = o; };
+      auto esink = [&](int own, int32_t ag, int32_t go, int32_t a0) {
+        goal = go;
+        total = reset_dists<true>(ag, go, a0, old_dist);
+        ret = 0.0; len = 0; ++episode; was_reset = true;
+#pragma unroll
+        for (int k = 0; k < NSC; ++k) so[k] = ost[own * G + k];
+#pragma unroll
+        for (int j = 0; j < NDC; ++j) { dp[j] = ost[own * G + NSC + j]; dgi[j] = j; }
+      };
+      if (!(m & (m - 1)))
+        wave_resets<WT, NSC, NDC, 1>(p, t, m, i, gid, episode, ax, ay, gxr, gyr, ncnt, xrows, wl, osink, esink);
+      else
+        wave_resets<WT, NSC, NDC, 64>(p, t, m, i, gid, episode, ax, ay, gxr, gyr, ncnt, xrows, wl, osink, esink);
+    }
+  }
+
+  // ---- state back to HBM, once
+  if (valid) {
+    p.agent[i] = pk(ax, ay);
+    p.prev_dist[i] = old_dist;
+    p.ep_return[i] = ret;
+    p.ep_len[i] = len;
+#pragma unroll
+    for (int j = 0; j < NDC; ++j) {
+      (p.dyn_obs + (size_t)j * N)[i] = dp[j];
+      (p.dyn_goal + (size_t)j * N)[i] = (uint8_t)dgi[j];
+    }
+    if (was_reset) {
+      p.goal[i] = goal;
+      p.total_dist[i] = total;
+      p.episode[i] = episode;
+#pragma unroll
+      for (int k = 0; k < NSC; ++k) (p.static_obs + (size_t)k * N)[i] = so[k];
+    }
+  }
+  if (slot && lane == 0) {
+    slot[0] = acc.n; slot[1] = acc.s1; slot[2] = acc.s2; slot[3] = acc.sl; slot[4] = acc.mn; slot[5] = acc.mx;
+  }
+  const uint32_t flags = valid ? st_flags : 0u;
+  if (__ballot(flags != 0u)) {
+    uint32_t f = flags;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) f |= (uint32_t)__shfl_xor((int)f, o);
+    if (lane == 0) atomicOr(p.status, (int)f);
+  }
+}
+
 __global__ void sample_actions_kernel(uint8_t* out, int32_t n, int32_t steps, int64_t env_offset,
                                       int32_t num_actions, unsigned long long seed) {
   int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -3530,6 +3771,25 @@ Launch pick_policy_rollout(const be_config& c, bool fixed_ok, int HT, int KS, in
   return L;
 }
 
+Launch pick_mlp_rollout(const be_config& c, bool fixed_ok, int layers, int waves) {
+  Launch L;
+  if (!fixed_shape(c, fixed_ok) || (layers != 2 && layers != 3)) return L;
+  switch (waves) {
+#define BE_CASE(nw)                                                                                  \
+    case nw:                                                                                         \
+      L.fnm = layers == 3 ? mlp_rollout_kernel<3, nw> : mlp_rollout_kernel<2, nw>;                   \
+      L.lds = layers == 3 ? MlpRollLds<3, nw>::bytes : MlpRollLds<2, nw>::bytes;                     \
+      break;
+    BE_CASE(1) BE_CASE(2) BE_CASE(4) BE_CASE(8)
+#undef BE_CASE
+    default: return L;
+  }
+  L.kind = KIND_MLP_ROLLOUT;
+  L.epb = 32 * waves; L.threads = 64 * waves;
+  snprintf(L.name, sizeof L.name, "mlp_rollout_kernel<%d, %d>", layers, waves);
+  return L;
+}
+
 Launch pick_pool_fill(int window) {
   Launch L;
   if (window != 10 && window != 5) return L;
@@ -3550,6 +3810,11 @@ void launch_kernel(const Launch& L, const KParams& a, hipStream_t stream) {
                        a);
   else
     hipLaunchKernelGGL(L.fn, grid, block, (size_t)L.lds, stream, a);
+}
+
+void launch_mlp_rollout(const Launch& L, const KParams& a, const MlpRollParams& q, hipStream_t stream) {
+  const dim3 grid((unsigned)((a.n + L.epb - 1) / L.epb)), block((unsigned)L.threads);
+  hipLaunchKernelGGL(L.fnm, grid, block, (size_t)L.lds, stream, a, q);
 }
 
 void launch_sample_actions(uint8_t* out, int32_t n, int32_t steps, int64_t env_offset, int32_t num_actions,

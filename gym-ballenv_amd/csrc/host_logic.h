@@ -1,7 +1,8 @@
 // host_logic.h -- the host side's logic that needs no HIP: the autoreset pool's bookkeeping, the
-// checkpoint blob's layout, be_pool_entry's word order and the per-step slice of a be_out.  Only
+// checkpoint blob's layout, be_pool_entry's word order, the per-step slice of a be_out, be_mlp_rollout's
+// instance rule and argument checks.  Only
 // ballenv.h, pool_layout.h and standard headers, so the host C++ compiler alone builds and tests it
-// (tests/host_logic_main.cpp); internal.h is the half that touches HIP.
+// (tests/host_logic_main.cpp, tests/mlp_rollout_host_main.cpp); internal.h is the half that touches HIP.
 #pragma once
 #include <stdint.h>
 #include <stdlib.h>
@@ -105,6 +106,38 @@ inline be_out be_out_at(const be_out& out, int64_t s, int64_t N, int64_t F) {
   if (o.final_return) o.final_return += s * N;
   if (o.final_len) o.final_len += s * N;
   return o;
+}
+
+// ---- be_mlp_rollout: waves per workgroup of the fused kernel (mlp_rollout_kernel<LAYERS, NW>)
+// A wave owns 32 envs and a workgroup stages the whole packed image, which leaves room for one workgroup
+// per compute unit: the largest NW of 8, 4, 2 whose full workgroups still give every compute unit one
+// (num_envs >= 32 NW cus), else 1 -- a batch too small for that runs one wave on as many units as it has
+// 32-env groups.  The same for both layer counts (`layers` is an argument so that a measured difference has
+// a place).  force: BALLENV_MLP_ROLLOUT_WAVES as be_mlp_create read it (-1: the rule; 0: no fused kernel,
+// the caller loops be_mlp_act + be_step; 1, 2, 4, 8: that instance).  Returns 0, 1, 2, 4 or 8.
+inline int mlp_rollout_waves(int64_t num_envs, int cus, int layers, int force = -1) {
+  if (force >= 0) return force;
+  if (num_envs < 1 || cus < 1 || (layers != 2 && layers != 3)) return 0;
+  for (int nw = 8; nw > 1; nw >>= 1)
+    if (num_envs >= (int64_t)32 * nw * cus) return nw;
+  return 1;
+}
+// BALLENV_MLP_ROLLOUT_WAVES: exactly one of 0, 1, 2, 4, 8, else (or unset) -1
+inline int mlp_rollout_waves_env(const char* v) {
+  if (!v || !v[0] || v[1]) return -1;
+  return (v[0] == '0' || v[0] == '1' || v[0] == '2' || v[0] == '4' || v[0] == '8') ? v[0] - '0' : -1;
+}
+// be_mlp_rollout's argument checks that need no device, in this order; NULL: fine, else the message.
+inline const char* mlp_rollout_args_error(const void* obs_last, int32_t steps, const be_out* out, const be_act_out* act) {
+  if (steps < 0) return "be_mlp_rollout: steps must be >= 0";
+  if (!out || !out->reward || !out->done) return "be_mlp_rollout needs out->reward and out->done";
+  if (!act || !act->action) return "be_mlp_rollout needs act->action";
+  if (!obs_last) return "be_mlp_rollout needs obs_last";
+  if ((uintptr_t)obs_last & 15) return "be_mlp_rollout: obs_last must be 16-byte aligned";
+  if (out->obs || out->obs_f32 || out->terminal_obs)
+    return "be_mlp_rollout: out->obs, obs_f32 and terminal_obs must be NULL (this agent reads no window rows)";
+  if (act->value || act->probs) return "be_mlp_rollout: act->value and act->probs must be NULL";
+  return nullptr;
 }
 
 // The optimiser arguments be_a2c_adam and be_mlp_opt share, checked in this order: the state, the Adam

@@ -128,3 +128,22 @@ struct be_pol_rollout_args {
 // The caller has entered the context's device.
 __attribute__((visibility("hidden"))) int be_internal_policy_rollout(be_ctx* ctx, const be_state* st,
                                                                      const be_pol_rollout_args* a, void* stream);
+
+// fused block-policy rollout (be_mlp_rollout -> mlp_rollout_kernel, then the observe kernel into obs_last)
+struct be_mlp_rollout_args {
+  const float* img;            // packed block-MLP image (device; mlp_core.h MlpLayout)
+  int32_t layers, waves;       // the instance: 2 | 3 layers, waves per workgroup (host_logic.h mlp_rollout_waves)
+  int32_t num_actions, final_relu;
+  unsigned long long seed;
+  uint8_t* obs_last;           // (N, F)
+  uint8_t* blocks_out;         // (steps, N, 29) or NULL
+  int32_t steps;
+  const be_out* out;           // per-step (steps, N) outputs
+  const be_act_out* act;       // (steps, N) action / log_prob
+};
+// 1: launched; 0: no fused kernel for this env shape / instance (the caller loops); < 0: error.
+// The caller has entered the context's device.
+__attribute__((visibility("hidden"))) int be_internal_mlp_rollout(be_ctx* ctx, const be_state* st,
+                                                                  const be_mlp_rollout_args* a, void* stream);
+// The instance name be_internal_mlp_rollout would launch (the calling thread's buffer), or NULL where it returns 0.
+__attribute__((visibility("hidden"))) const char* be_internal_mlp_rollout_name(be_ctx* ctx, int32_t layers, int32_t waves);

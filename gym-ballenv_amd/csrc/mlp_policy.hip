@@ -12,11 +12,14 @@
 //   be_mlp_load   one launch: the f32 state_dict arrays into the padded image the kernel stages
 //   be_mlp_act    one launch: [prep_state2 ->] forward -> softmax -> draw, the arithmetic
 //                 include/ballenv.h pins
+//   be_mlp_rollout  `steps` steps of be_mlp_act + be_step: one launch of ballenv.hip's mlp_rollout_kernel and
+//                 the observe kernel, or that loop where no fused instance applies
 //   be_mlp_opt    two launches: optimizer.step() of both training loops (Adam, ball_env_reinforce.py:196;
 //                 SGD, train_supervise.py:75) on the state_dict tensors in place, fused with be_mlp_load's
 //                 pack of the new weights; then the one-wave state kernel it shares with
 //                 be_a2c_adam (be_internal_optim_advance)
 //
+// The image's layout and the forward itself are mlp_core.h's, shared with the fused rollout.
 // Every product runs on v_mfma_f32_16x16x4_f32 (an exact f32 fma chain) as D = W . x^T: the
 // weights are the A operand (row = output unit), a tile of 16 envs the B operand (column = env),
 // so lane (c = lane & 15, g = lane >> 4) ends a layer holding units 16 t + 4 g + r (r = 0..3) of
@@ -41,59 +44,22 @@
 #include <math.h>
 #include <new>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include "ballenv.h"
 #include "blocks_core.h"
 #include "host_logic.h"
 #include "internal.h"
+#include "mlp_core.h"
 #include "optim_core.h"
 #include "philox.h"
 #include "policy_core.h"
 
 namespace {
 
-#ifndef BE_MLP_WAVES
-#define BE_MLP_WAVES 8       // -DBE_MLP_WAVES=n: timing builds with n waves per workgroup
-#endif
-constexpr int MLP_NW = BE_MLP_WAVES, MLP_THREADS = 64 * MLP_NW;
+constexpr int MLP_THREADS = 64 * MLP_NW;
 constexpr int MLP_TILE = 16;                 // envs per wave and tile
-constexpr int MLP_MAXH = 128, MLP_KS1 = 8;   // 4-wide k steps of layer 1 (29 -> 32 inputs)
-constexpr int MLP_NO = 16;                   // padded outputs: policy_finish<16> (actions 0..14, slot 15 unused)
-constexpr int MLP_ZP = 17;                   // row stride of a tile's logits in the wave's slice
-constexpr int MLP_SLICE = 16 * MLP_ZP + 16 * BLK_ROW / 4 + 12;   // floats per wave: logits, then 16 rows of blocks
 constexpr int MLP_CH = 5;                    // obstacles per lane and load chunk (4 groups: 20 per pass)
-static_assert(MLP_SLICE % 4 == 0 && 16 * BLK_ROW % 4 == 0, "the slices stay 16-byte aligned");
-static_assert(POL_MAXA < MLP_NO, "policy_finish<16> holds be_policy_create's action bound");
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// The packed image, identical in HBM and in each workgroup's LDS (offsets in floats).  HT1 / HT2 / HTL
-// are 16-row tiles of hidden1 / hidden2 / the last layer's input; l15 = lane & 15, l4 = lane >> 4.
-struct MlpLayout {
-  int layers, HT1, HT2, HTL;
-  int f1;      // [MLP_KS1][HT1][64]   W1[16 t + l15][4 k + l4]
-  int b1;      // [16 HT1]
-  int f2;      // [4 HT1][HT2][64]     W2[16 t + l15][16 (s >> 2) + 4 l4 + (s & 3)]     (3 layers)
-  int b2;      // [16 HT2]                                                               (3 layers)
-  int f3;      // [4 HTL][64]          W_last[l15][16 (s >> 2) + 4 l4 + (s & 3)]
-  int b3;      // [16]
-  int hb;      // [16]                 0 for an action (and slot 15), -inf for a pad action
-  int total, lds;                      // floats of the image; bytes of LDS with the waves' slices
-};
-__host__ __device__ constexpr MlpLayout mlp_layout(int layers, int HT1, int HT2) {
-  MlpLayout L{};
-  L.layers = layers; L.HT1 = HT1; L.HT2 = layers == 3 ? HT2 : 0; L.HTL = layers == 3 ? HT2 : HT1;
-  L.f1 = 0;
-  L.b1 = L.f1 + MLP_KS1 * HT1 * 64;
-  L.f2 = L.b1 + 16 * HT1;
-  L.b2 = L.f2 + 4 * HT1 * L.HT2 * 64;
-  L.f3 = L.b2 + 16 * L.HT2;
-  L.b3 = L.f3 + 4 * L.HTL * 64;
-  L.hb = L.b3 + 16;
-  L.total = L.hb + 16;
-  L.lds = (L.total + MLP_NW * MLP_SLICE) * 4;
-  return L;
-}
 
 struct MPack {               // device f32 weights in torch state_dict layout; wl / bl: the last layer
   const float *w1, *b1, *w2, *b2, *wl, *bl;
@@ -245,55 +211,6 @@ struct MParams {
   int32_t n, ns, nd, ntiles, A, gid0, final_relu;
 };
 
-// sum of x over lanes l, l^16, l^32, l^48 (or_groups of policy_core.h with +)
-__device__ __forceinline__ uint32_t sum_groups_u32(uint32_t x) {
-  const auto a = __builtin_amdgcn_permlane16_swap(x, x, false, false);
-  x = a[0] + a[1];
-  const auto b = __builtin_amdgcn_permlane32_swap(x, x, false, false);
-  return b[0] + b[1];
-}
-
-// wave barrier between a slice's writes and its reads by other lanes of the wave
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-#define BE_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
-
-// One layer with HTI input tiles (h, relu'd, in the accumulator layout) and HTO output tiles:
-// acc[t] starts at the bias.  frag: [4 HTI][HTO][64], bias: [16 HTO].
-template <int HTI, int HTO>
-__device__ __forceinline__ void mlp_hidden(const float* frag, const float* bias, const f32x4 (&h)[HTI], int lane,
-                                           f32x4 (&acc)[HTO]) {
-#pragma unroll
-  for (int t = 0; t < HTO; ++t) acc[t] = *(const f32x4*)(bias + 16 * t + 4 * (lane >> 4));
-#pragma unroll
-  for (int hp = 0; hp < HTI; ++hp)
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-      for (int t = 0; t < HTO; ++t) acc[t] = BE_MFMA(frag[((hp * 4 + r) * HTO + t) * 64 + lane], h[hp][r], acc[t]);
-#pragma unroll
-  for (int t = 0; t < HTO; ++t)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) acc[t][r] = fmaxf(acc[t][r], 0.0f);
-}
-
-// The last layer: one output tile, four fma chains (chain r takes the steps (t, r); chain 0 starts at
-// the bias), z = (c0 + c1) + (c2 + c3).
-template <int HTI>
-__device__ __forceinline__ f32x4 mlp_last(const float* frag, const float* bias, const f32x4 (&h)[HTI], int lane) {
-  const f32x4 zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
-  f32x4 c[4] = {*(const f32x4*)(bias + 4 * (lane >> 4)), zero4, zero4, zero4};
-#pragma unroll
-  for (int hp = 0; hp < HTI; ++hp)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) c[r] = BE_MFMA(frag[(hp * 4 + r) * 64 + lane], h[hp][r], c[r]);
-  return (c[0] + c[1]) + (c[2] + c[3]);
-}
-
 template <int LAYERS, int HT1, int HT2>
 __global__ __launch_bounds__(MLP_THREADS) void mlp_act_kernel(MParams p) {
   extern __shared__ uint4 mlp_lds[];
@@ -372,7 +289,8 @@ __global__ __launch_bounds__(MLP_THREADS) void mlp_act_kernel(MParams p) {
       }
     }
 
-    // 2: the layers
+    // 2: the layers (mlp_core.h)
+    // (layer 1 keeps its inline text here: moved into a helper in mlp_core.h, the kernel's schedule changes)
     f32x4 h1[HT1];
 #pragma unroll
     for (int t = 0; t < HT1; ++t) h1[t] = *(const f32x4*)(W + L.b1 + 16 * t + 4 * l4);
@@ -409,9 +327,6 @@ __global__ __launch_bounds__(MLP_THREADS) void mlp_act_kernel(MParams p) {
   }
 }
 
-// Every shape runs the instance of its layer count, padded to 128 hidden units.
-constexpr int MLP_HT = MLP_MAXH / 16;
-
 }  // namespace
 
 struct be_mlp {
@@ -421,6 +336,7 @@ struct be_mlp {
   MlpLayout L;
   float* img;
   bool loaded;
+  int roll_waves;            // BALLENV_MLP_ROLLOUT_WAVES at be_mlp_create (-1: host_logic.h's rule)
 };
 
 extern "C" {
@@ -441,6 +357,7 @@ int be_mlp_create(be_ctx* ctx, int32_t layers, int32_t hidden1, int32_t hidden2,
   m->ctx = ctx; m->cv = be_ctx_get(ctx);
   m->layers = layers; m->H1 = hidden1; m->H2 = hidden2; m->A = num_actions; m->final_relu = final_relu ? 1 : 0;
   m->L = mlp_layout(layers, MLP_HT, MLP_HT);
+  m->roll_waves = behost::mlp_rollout_waves_env(getenv("BALLENV_MLP_ROLLOUT_WAVES"));   // (A/B runs and tests)
   const DeviceGuard dg(m->cv.device);   // the caller's current device is restored on return
   hipError_t e = dg.err;
   if (e == hipSuccess) e = hipDeviceGetAttribute(&m->cus, hipDeviceAttributeMultiprocessorCount, m->cv.device);
@@ -556,6 +473,42 @@ int be_mlp_act(be_mlp* m, const be_state* st, const uint8_t* blocks_in, uint8_t*
   else
     hipLaunchKernelGGL((mlp_act_kernel<2, MLP_HT, 0>), grid, block, (size_t)m->L.lds, (hipStream_t)stream, p);
   return be_launched(be_ctx_err(ctx));
+}
+
+// ball_env_reinforce.py's episode loop (:309-336: prep_state2, select_action, env.step, the reward appended)
+// for every env, `steps` steps per call.
+int be_mlp_rollout(be_mlp* m, const be_state* st, uint8_t* obs_last, uint8_t* blocks_out, int32_t steps,
+                   const be_out* out, const be_act_out* act, uint64_t seed, void* stream) {
+  if (!m) return be_ctx_fail(nullptr, BE_E_INVALID, "be_mlp_rollout: mlp is NULL");
+  be_ctx* ctx = m->ctx;
+  if (!m->loaded) return be_ctx_fail(ctx, BE_E_INVALID, "be_mlp_rollout before be_mlp_load");
+  if (int rc = be_ctx_check_state(ctx, st)) return rc;
+  if (const char* msg = behost::mlp_rollout_args_error(obs_last, steps, out, act)) return be_ctx_fail(ctx, BE_E_INVALID, msg);
+  if (steps == 0) return BE_OK;
+  BE_ENTER_DEVICE(be_ctx_err(ctx), m->cv.device);
+  const int waves = behost::mlp_rollout_waves(m->cv.num_envs, m->cus, m->layers, m->roll_waves);
+  if (waves > 0) {
+    const be_mlp_rollout_args r{m->img, m->layers, waves, m->A, m->final_relu, (unsigned long long)seed,
+                                obs_last, blocks_out, steps, out, act};
+    const int rc = be_internal_mlp_rollout(ctx, st, &r, stream);
+    if (rc != 0) return rc < 0 ? rc : BE_OK;
+  }
+  // no fused kernel for this shape: be_mlp_act + be_step per step (the same trajectory)
+  const int64_t N = m->cv.num_envs, F = 4 + (int64_t)m->cv.window * m->cv.window;
+  for (int32_t s = 0; s < steps; ++s) {
+    const be_act_out ao{act->action + s * N, act->log_prob ? act->log_prob + s * N : nullptr, nullptr, nullptr};
+    if (int e = be_mlp_act(m, st, nullptr, blocks_out ? blocks_out + s * N * BLK_ROW : nullptr, &ao, seed, stream)) return e;
+    be_out o = behost::be_out_at(*out, s, N, F);
+    o.obs = obs_last;
+    if (int e = be_step(ctx, st, ao.action, nullptr, nullptr, &o, stream)) return e;
+  }
+  return BE_OK;
+}
+
+const char* be_mlp_rollout_kernel(const be_mlp* m) {
+  if (!m) return nullptr;
+  const int waves = behost::mlp_rollout_waves(m->cv.num_envs, m->cus, m->layers, m->roll_waves);
+  return waves > 0 ? be_internal_mlp_rollout_name(m->ctx, m->layers, waves) : nullptr;
 }
 
 int64_t be_mlp_bytes(const be_mlp* m) { return m ? (int64_t)m->L.total * 4 : 0; }

@@ -84,6 +84,16 @@ struct KParams {
   uint32_t* pool;
 };
 
+// mlp_rollout_kernel's own arguments, beside the KParams of the call (be_mlp_rollout)
+struct MlpRollParams {
+  const float* img;            // packed block-MLP image (mlp_core.h MlpLayout)
+  uint8_t* blocks_out;         // (steps, N, 29) or NULL: the counts each action was drawn from
+  uint8_t* action;             // (steps, N)
+  float* log_prob;             // (steps, N) or NULL
+  unsigned long long seed;
+  int32_t num_actions, final_relu;
+};
+
 // step2_kernel's arguments (launch_kernel fills all three from the one KParams of the call):
 //  * 14 dwords of leading scalars.  gfx950's dispatcher preloads them into user SGPRs while the
 //    wave launches (-amdgpu-kernarg-preload-count, build.py; a by-value struct is not preloaded),
@@ -118,6 +128,7 @@ constexpr int64_t FIX_MAX_ENVS = 1ll << 29;
 using KFn = void (*)(KParams);
 // step2_kernel: its leading scalar arguments (preloaded into SGPRs), KHot, then the KParams
 using KFn2 = void (*)(const Tables*, uint32_t*, int32_t*, int32_t*, uint8_t*, int32_t*, int32_t, int32_t, KHot, KParams);
+using KFnMlp = void (*)(KParams, MlpRollParams);   // mlp_rollout_kernel
 enum Kind {
   KIND_NONE = 0,         // no kernel for this config (Launch::ok() is false)
   KIND_GENERIC,          // be_kernel<W or 0, mode>: any config, step / reset / observe
@@ -126,19 +137,25 @@ enum Kind {
   KIND_LANES,            // stepw_kernel / rolloutw_kernel: fixed shape at W = 5, 4 or 8 lanes per env
   KIND_ROLLOUT,          // rollout_kernel: the fused multi-step rollout
   KIND_POLICY_ROLLOUT,   // rollout_kernel with the policy in the loop
+  KIND_MLP_ROLLOUT,      // mlp_rollout_kernel: the block-count policy and the step in one kernel
   KIND_POOL_FILL         // pool_fill_kernel
 };
 struct Launch {
   KFn fn = nullptr;
   KFn2 fn2 = nullptr;            // step2_kernel (fn is nullptr then)
   KFn2 fn2_recompute = nullptr;  // its KParams::prev_read = 0 instance (A/B only; launch_kernel picks by the flag)
+  KFnMlp fnm = nullptr;          // mlp_rollout_kernel (fn and fn2 are nullptr then; launch_mlp_rollout)
   int kind = KIND_NONE;
   int epb = BLOCK_THREADS;       // envs per block
   int threads = BLOCK_THREADS;
   int lds = 0;                   // dynamic LDS bytes: the kernel's own layout (its *Lds struct)
   bool consumes_pool = false;    // a step kernel whose `pool` instance copies autoreset-pool entries
   char name[48] = {0};
-  bool ok() const { return fn || fn2; }
+  bool ok() const { return fn || fn2 || fnm; }
+  // the device function, for hipFuncGetAttributes
+  const void* entry() const {
+    return fn ? reinterpret_cast<const void*>(fn) : (fn2 ? reinterpret_cast<const void*>(fn2) : reinterpret_cast<const void*>(fnm));
+  }
 };
 #define BE_HIDDEN __attribute__((visibility("hidden")))
 // fixed_ok: the context's part of the fixed-shape preconditions (unit moves, pairwise-distinct goals,
@@ -153,6 +170,10 @@ BE_HIDDEN Launch pick_kernel(const be_config& c, int mode, bool fixed_ok = false
 // kernel's Policy(W) shapes (H 208 / W 10 and H 128 / W 5, 9 actions); !ok(): not applicable.
 BE_HIDDEN Launch pick_rollout(const be_config& c, bool fixed_ok, int lpe5 = 0);
 BE_HIDDEN Launch pick_policy_rollout(const be_config& c, bool fixed_ok, int HT, int KS, int NO);
+// The fused block-policy rollout for the fixed env shape (any window: it writes no observation), one
+// instance per layer count (2, 3) and waves per workgroup (1, 2, 4, 8); !ok(): not applicable.
+BE_HIDDEN Launch pick_mlp_rollout(const be_config& c, bool fixed_ok, int layers, int waves);
+BE_HIDDEN void launch_mlp_rollout(const Launch& L, const KParams& a, const MlpRollParams& q, hipStream_t stream);
 BE_HIDDEN Launch pick_pool_fill(int window);   // window 10 or 5 (the kernels with consumes_pool)
 // The one place a step-engine kernel is launched: ceil(a.n / L.epb) blocks of L.threads, L.lds bytes.
 BE_HIDDEN void launch_kernel(const Launch& L, const KParams& a, hipStream_t stream);

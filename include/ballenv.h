@@ -357,6 +357,27 @@ int be_mlp_load(be_mlp* mlp, const float* w1, const float* b1, const float* w2, 
  * NULL (BE_E_INVALID).  One launch, asynchronous on stream, graph-capturable.                    */
 int be_mlp_act(be_mlp* mlp, const be_state* st, const uint8_t* blocks_in, uint8_t* blocks_out, const be_act_out* out,
                uint64_t seed, void* stream);
+/* `steps` steps of the REINFORCE agent's episode loop (examples/ball_env_reinforce.py:309-336: prep_state2,
+ * select_action, env.step, the reward appended) for every env in one launch: for s in 0..steps-1
+ *   act[s] = be_mlp_act(state) (the same pinned arithmetic, the same Philox draw);  be_step(act[s])
+ * act: (steps, N) action (required) and log_prob (optional); act->value and act->probs must be NULL.
+ * blocks_out (steps, N, 29) u8 or NULL: row s holds the counts action s was drawn from.  out: per-step
+ * (steps, N) outputs as for be_rollout -- reward and done required, truncated / final_return / final_len
+ * optional, stats accumulates as for be_step; out->obs, obs_f32 and terminal_obs must be NULL (this
+ * agent reads no window rows; a caller who wants them per step runs the loop).  obs_last (N, 4+W*W),
+ * required and 16-byte aligned, receives the window obs of the final state: what the loop's last
+ * be_step writes.  steps == 0: BE_OK, no launch.  A handle never loaded and never stepped by be_mlp_opt
+ * is rejected, as by be_mlp_act.  Bit-identical to the be_mlp_act + be_step loop in everything it
+ * leaves (the outputs, the whole be_state, the stats slots, the status word, obs_last).
+ * The fixed env shape (13 + 5 obstacles, unit moves, distinct goals, action indices, Philox mode) runs
+ * one kernel with the packed weights in LDS and each env's state in registers, then the observe
+ * kernel; other shapes run that loop.  Asynchronous on stream, graph-capturable, allocates nothing. */
+int be_mlp_rollout(be_mlp* mlp, const be_state* st, uint8_t* obs_last, uint8_t* blocks_out, int32_t steps,
+                   const be_out* out, const be_act_out* act, uint64_t seed, void* stream);
+/* The fused kernel's instance name for this handle (the calling thread's buffer, valid until its next
+ * call), or NULL when be_mlp_rollout runs the loop.  BALLENV_MLP_ROLLOUT_WAVES = 0 | 1 | 2 | 4 | 8, read at
+ * be_mlp_create, forces the loop or one instance (A/B runs).                                       */
+const char* be_mlp_rollout_kernel(const be_mlp* mlp);
 /* Bytes of the packed weight image (staged once per workgroup in LDS). */
 int64_t be_mlp_bytes(const be_mlp* mlp);
 
