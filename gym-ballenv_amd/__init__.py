@@ -38,6 +38,9 @@ def __getattr__(name):
                 "SupervisedTrainer"):
         from . import block_policy
         return getattr(block_policy, name)
+    if name in ("PixelPolicy", "pixel_inputs"):
+        from . import pixel_policy
+        return getattr(pixel_policy, name)
     if name == "BatchedBoard":
         from .board import BatchedBoard
         return BatchedBoard
@@ -53,4 +56,4 @@ __all__ = ["EnvConfig", "MOVE_LIST", "step_bytes", "survey_step_bytes", "Box", "
            "A2CGrad", "HipAdam", "A2CTrainer", "BatchedBoard", "BlockPolicy", "HipBlockPolicy", "BlockRollout",
            "torch_block_select_action", "reinforce_losses", "reinforce_update", "reference_block_weights",
            "BlockGrad", "supervised_losses", "supervised_update", "reference_supervise_data", "HipBlockOptim",
-           "BlockTrainer", "SupervisedTrainer"]
+           "BlockTrainer", "SupervisedTrainer", "PixelPolicy", "pixel_inputs"]

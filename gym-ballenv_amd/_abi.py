@@ -27,7 +27,7 @@ EXPORTS = ("be_abi_version", "be_config_default", "be_config_check", "be_step_by
            "be_create", "be_destroy", "be_reset", "be_step", "be_step_n", "be_rollout", "be_observe", "be_sample_actions",
            "be_status", "be_state_blob_bytes", "be_save_state", "be_load_state",
            "be_pool_fill", "be_pool_invalidate", "be_pool_set_period", "be_pool_period", "be_pool_bytes", "be_pool_entry", "be_policy_create", "be_policy_destroy", "be_policy_load", "be_policy_act",
-           "be_policy_rollout", "be_policy_bytes", "be_observe_blocks",
+           "be_policy_rollout", "be_policy_bytes", "be_observe_blocks", "be_observe_pixels", "be_pixels_coeffs",
            "be_mlp_create", "be_mlp_destroy", "be_mlp_load", "be_mlp_act", "be_mlp_bytes",
            "be_mlp_rollout", "be_mlp_rollout_kernel",
            "be_mlp_grad_workspace_bytes", "be_mlp_grad", "be_mlp_opt",
@@ -194,6 +194,8 @@ def lib() -> C.CDLL:
         "be_policy_rollout": (C.c_int, [vp, P(BeState), vp, vp, i32, P(BeOut), P(BeActOut), u64, vp]),
         "be_policy_bytes": (i64, [vp]),
         "be_observe_blocks": (C.c_int, [vp, P(BeState), vp, vp, vp]),
+        "be_observe_pixels": (C.c_int, [vp, P(BeState), vp, vp, vp, vp]),
+        "be_pixels_coeffs": (C.c_int, [P(i32), P(i32)]),
         "be_mlp_create": (C.c_int, [vp, i32, i32, i32, i32, i32, P(vp)]),
         "be_mlp_destroy": (C.c_int, [vp]),
         "be_mlp_load": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp]),
@@ -228,7 +230,7 @@ def lib() -> C.CDLL:
     for name, (res, args) in sig.items():
         fn = getattr(L, name, None)
         if fn is None and diag and (name.startswith("be_pool_") or name.startswith("be_mlp_") or
-                                     name in ("be_board_pool_bytes", "be_a2c_adam")):
+                                     name in ("be_board_pool_bytes", "be_a2c_adam", "be_observe_pixels", "be_pixels_coeffs")):
             continue
         if fn is None:
             raise BallEnvError(f"{LIB_PATH} does not export {name}: rebuild it")

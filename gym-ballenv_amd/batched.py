@@ -302,6 +302,33 @@ class BatchedBallEnv:
         _abi.check(self._lib.be_observe_blocks(self._ctx, C.byref(self._st), u8, f, self._stream()), self._ctx)
         return out
 
+    PIXEL_PATCH, PIXEL_SIZE = 100, 40    # extract_patch's patch and image sides (ball_cnn_reinforce.py:120-125)
+
+    def observe_pixels(self, f32: bool = False, patch: bool = False, out=None):
+        """extract_patch of examples/ball_cnn_reinforce.py:120-163 for the current state (no state
+        change): the rendered frame padded with white, the 100 x 100 patch centred on the agent,
+        PIL's bicubic resize to 40 x 40 -- the pixel agent's image, (N, 3, 40, 40) u8, or f32 in
+        [0, 1] (ToTensor) with ``f32=True``.  ``patch=True`` returns ``(image, patch)`` with the
+        (N, 100, 100, 3) u8 patch before the resize.  ``out``: the tensor (or, with ``patch``, the
+        pair of tensors) to write into instead of allocating; it is returned.  One launch on the
+        current stream."""
+        N, S, P = self.num_envs, self.PIXEL_SIZE, self.PIXEL_PATCH
+        dt = torch.float32 if f32 else torch.uint8
+        if out is None:
+            img = torch.empty(N, 3, S, S, dtype=dt, device=self.device)
+            pt = torch.empty(N, P, P, 3, dtype=torch.uint8, device=self.device) if patch else None
+        else:
+            img, pt = out if patch else (out, None)
+            for t, shape, d, name in ((img, (N, 3, S, S), dt, "out image"), (pt, (N, P, P, 3), torch.uint8, "out patch")):
+                if t is None:
+                    continue
+                self._check_shape(t, shape, name)
+                if t.dtype != d or t.device != self.device or not t.is_contiguous():
+                    raise ValueError(f"{name}: expected a contiguous {d} tensor on {self.device}")
+        u8, f = (None, img.data_ptr()) if f32 else (img.data_ptr(), None)
+        _abi.check(self._lib.be_observe_pixels(self._ctx, self._st_ref, _ptr(pt), u8, f, self._stream_int()), self._ctx)
+        return (img, pt) if patch else img
+
     def window_only(self) -> torch.Tensor:
         """(N, W*W) view of the window part of the obs: prep_state4 as the potential-field
         planners define it, without the quadrant (examples/potential_fields_modified.py:66-93)."""

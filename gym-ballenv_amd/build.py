@@ -14,6 +14,9 @@ object) and linked into one shared library:
   csrc/policy.hip   select_action kernel (-fno-slp-vectorize: scalar f32 FMAs
                     interleave better with MFMAs than SLP-packed ones on gfx950)
   csrc/features.hip sibling observation formats (prep_state2 block counts)
+  csrc/pixels.hip   the pixel agent's observation (extract_patch: the 100 x 100 patch around the agent as row
+                    bitmasks, PIL's bicubic resize to 40 x 40 byte for byte); its host half without HIP --
+                    PIL's coefficients, the argument checks -- is csrc/pixels_host.h (CPU-tested)
   csrc/board.hip    the createBoard physics profile + featureExtractor
   csrc/a2c.hip      A2C targets of a recorded rollout (the batched finish_episode)
   csrc/a2c_grad.hip A2C losses and Policy gradients of recorded rows (f32 MFMAs; no VGPR_MFMA:
@@ -59,10 +62,10 @@ VGPR_MFMA = ["-mllvm", "-amdgpu-mfma-vgpr-form"]
 # prologue); the compiler keeps an s_load entry for firmware without the preload.
 KARG_PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
 UNITS = {"ballenv.hip": [*VGPR_MFMA, *KARG_PRELOAD], "abi.hip": [], "policy.hip": ["-fno-slp-vectorize", *VGPR_MFMA],
-         "features.hip": [], "board.hip": [], "a2c.hip": [], "a2c_grad.hip": [], "a2c_adam.hip": [],
+         "features.hip": [], "pixels.hip": [], "board.hip": [], "a2c.hip": [], "a2c_grad.hip": [], "a2c_adam.hip": [],
          "mlp_policy.hip": [], "mlp_grad.hip": []}
 HEADERS = [HDR, *(os.path.join(CSRC, h) for h in ("philox.h", "internal.h", "host_logic.h", "pool_layout.h", "policy_core.h", "blocks_core.h", "mlp_core.h", "diag.h",
-                                              "step_types.h", "optim_core.h"))]
+                                              "step_types.h", "optim_core.h", "pixels_host.h"))]
 
 
 def _stale(out, deps):

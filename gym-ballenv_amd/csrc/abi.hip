@@ -90,6 +90,8 @@ be_ctx_view be_ctx_get(const be_ctx* ctx) {
   v.num_envs = ctx->cfg.num_envs; v.window = ctx->cfg.window; v.device = ctx->device;
   v.num_static = ctx->cfg.num_static; v.num_dynamic = ctx->cfg.num_dynamic;
   v.env_offset = ctx->cfg.env_offset;
+  v.screen_width = ctx->cfg.screen_width; v.screen_height = ctx->cfg.screen_height;
+  v.radius_obstacle = ctx->cfg.radius_obstacle; v.radius_agent = ctx->cfg.radius_agent;
   return v;
 }
 int be_ctx_check_state(be_ctx* ctx, const be_state* st) {

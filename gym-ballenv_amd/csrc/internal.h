@@ -81,6 +81,7 @@ inline hipError_t be_pool_alloc(uint32_t** pool, int64_t bytes) {
 struct be_ctx_view {
   int32_t num_envs, window, device, num_static, num_dynamic;
   int64_t env_offset;
+  int32_t screen_width, screen_height, radius_obstacle, radius_agent;   // what a frame of the env shows (pixels.hip)
 };
 __attribute__((visibility("hidden"))) be_ctx_view be_ctx_get(const be_ctx* ctx);
 // ctx's last-error buffer (the calling thread's own for a NULL ctx), and msg recorded in it; returns code

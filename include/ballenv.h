@@ -323,6 +323,25 @@ int64_t be_policy_bytes(const be_policy* pol);
  * in its 20-px block of the 5x5 grid -- as u8 (out) and/or f32 (out_f32; NULL = skip). */
 int be_observe_blocks(be_ctx* ctx, const be_state* st, uint8_t* out, float* out_f32, void* stream);
 
+/* extract_patch of examples/ball_cnn_reinforce.py:120-163 for every env's current state (no state
+ * change): the frame BallEnv.render draws (gym_ballenv/envs/ballenv_env.py:357-386: agent disk and
+ * goal fan black, static disks red, dynamic disks green, on white), padded with white, cut to the
+ * 100 x 100 patch centred on the agent and resized to 40 x 40 with PIL's bicubic filter.
+ *   patch    (N, 100, 100, 3) u8, HWC, top row first: cell (i, j) is world pixel
+ *            x = ax - 50 + j, y = ay + 49 - i; white outside the screen
+ *   out      (N, 3, 40, 40) u8, CHW: Image.fromarray(patch).resize((40, 40), Image.BICUBIC), byte
+ *            for byte (a horizontal pass into a u8 intermediate, then a vertical one; 22-bit
+ *            fixed-point coefficients, be_pixels_coeffs)
+ *   out_f32  (N, 3, 40, 40) f32: ToTensor's out / 255 (f32 division)
+ * Any subset: a NULL pointer skips that output, all three NULL is BE_E_INVALID.  Every pointer is
+ * 16-byte aligned.  The reference then passes the HWC tensor through ToPILImage, which reads it
+ * as CHW; that quirk is not reproduced.  One launch, no allocation: capturable. */
+int be_observe_pixels(be_ctx* ctx, const be_state* st, uint8_t* patch, uint8_t* out, float* out_f32, void* stream);
+/* The resize's coefficients, 100 -> 40 (PIL's precompute_coeffs + normalize_coeffs_8bpc): kk
+ * (40, 10) i32, zero behind a row's taps; bounds (40, 2) i32, first input index and tap count.
+ * Pure host code, no device. */
+int be_pixels_coeffs(int32_t* kk, int32_t* bounds);
+
 /* ---- on-GPU select_action of the REINFORCE / supervised agents (the block-count MLP) ----
  * Replaces, for every env at once, the caller's per-step
  *   probs = Policy()(prep_state2(state))                examples/ball_env_reinforce.py:57-73, 130-172
