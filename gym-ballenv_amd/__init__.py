@@ -38,7 +38,8 @@ def __getattr__(name):
                 "SupervisedTrainer"):
         from . import block_policy
         return getattr(block_policy, name)
-    if name in ("PixelPolicy", "pixel_inputs"):
+    if name in ("PixelPolicy", "pixel_inputs", "HipPixelPolicy", "PixelRollout", "torch_pixel_forward",
+                "torch_pixel_select_action", "reference_pixel_weights"):
         from . import pixel_policy
         return getattr(pixel_policy, name)
     if name == "BatchedBoard":
@@ -56,4 +57,5 @@ __all__ = ["EnvConfig", "MOVE_LIST", "step_bytes", "survey_step_bytes", "Box", "
            "A2CGrad", "HipAdam", "A2CTrainer", "BatchedBoard", "BlockPolicy", "HipBlockPolicy", "BlockRollout",
            "torch_block_select_action", "reinforce_losses", "reinforce_update", "reference_block_weights",
            "BlockGrad", "supervised_losses", "supervised_update", "reference_supervise_data", "HipBlockOptim",
-           "BlockTrainer", "SupervisedTrainer", "PixelPolicy", "pixel_inputs"]
+           "BlockTrainer", "SupervisedTrainer", "PixelPolicy", "pixel_inputs", "HipPixelPolicy", "PixelRollout",
+           "torch_pixel_forward", "torch_pixel_select_action", "reference_pixel_weights"]

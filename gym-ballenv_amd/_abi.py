@@ -31,6 +31,7 @@ EXPORTS = ("be_abi_version", "be_config_default", "be_config_check", "be_step_by
            "be_mlp_create", "be_mlp_destroy", "be_mlp_load", "be_mlp_act", "be_mlp_bytes",
            "be_mlp_rollout", "be_mlp_rollout_kernel",
            "be_mlp_grad_workspace_bytes", "be_mlp_grad", "be_mlp_opt",
+           "be_cnn_create", "be_cnn_destroy", "be_cnn_load", "be_cnn_act", "be_cnn_bytes",
            "be_board_config_default", "be_board_create", "be_board_destroy", "be_board_last_error",
            "be_board_reset", "be_board_step", "be_board_rollout", "be_board_observe", "be_board_status",
            "be_board_pool_bytes")
@@ -111,6 +112,19 @@ class BeMlpTensors(C.Structure):
 
 
 MLP_OPT_ADAM, MLP_OPT_SGD = 0, 1
+
+# be_cnn_weights: the pixel agent's 20 state_dict tensors, in this order
+CNN_TENSORS = tuple(f"{m}.{w}" for i in (1, 2, 3)
+                    for m, ws in ((f"conv{i}", ("weight", "bias")),
+                                  (f"bn{i}", ("weight", "bias", "running_mean", "running_var")))
+                    for w in ws) + ("head.weight", "head.bias")
+
+
+class BeCnnWeights(C.Structure):
+    _fields_ = [(k.replace(".", "_"), C.c_void_p) for k in CNN_TENSORS]
+
+
+CNN_NORM_SAMPLE, CNN_NORM_RUNNING = 0, 1
 
 
 class BeA2CTensors(C.Structure):
@@ -208,6 +222,11 @@ def lib() -> C.CDLL:
                                   vp]),
         "be_mlp_opt": (C.c_int, [vp, i32, P(BeMlpTensors), P(BeMlpTensors), P(BeMlpTensors), P(BeMlpTensors), vp,
                                  C.c_double, C.c_double, C.c_double, vp, vp, i32, vp]),
+        "be_cnn_create": (C.c_int, [vp, i32, P(vp)]),
+        "be_cnn_destroy": (C.c_int, [vp]),
+        "be_cnn_load": (C.c_int, [vp, P(BeCnnWeights), vp]),
+        "be_cnn_act": (C.c_int, [vp, P(BeState), vp, vp, i32, P(BeActOut), u64, vp]),
+        "be_cnn_bytes": (i64, [vp]),
         "be_a2c_targets": (C.c_int, [vp, vp, vp, vp, vp, i32, C.c_double, C.c_double, P(BeA2COut), vp]),
         "be_a2c_grad_workspace_bytes": (i64, [vp, i32, i32]),
         "be_a2c_grad": (C.c_int, [vp, vp, vp, vp, vp, i64, P(BeA2CWeights), vp, i64, P(BeA2CGrads), vp]),
@@ -229,7 +248,7 @@ def lib() -> C.CDLL:
     diag = bool(os.environ.get("BALLENV_LIB"))
     for name, (res, args) in sig.items():
         fn = getattr(L, name, None)
-        if fn is None and diag and (name.startswith("be_pool_") or name.startswith("be_mlp_") or
+        if fn is None and diag and (name.startswith("be_pool_") or name.startswith("be_mlp_") or name.startswith("be_cnn_") or
                                      name in ("be_board_pool_bytes", "be_a2c_adam", "be_observe_pixels", "be_pixels_coeffs")):
             continue
         if fn is None:

@@ -37,6 +37,10 @@ object) and linked into one shared library:
   csrc/mlp_grad.hip the block-count MLP's REINFORCE / cross-entropy losses and gradients of recorded rows
                     (f32 MFMAs; no VGPR_MFMA, for a2c_grad.hip's reason: the gradient accumulators live
                     for the whole kernel, the AGPR half of the register file is where they belong)
+  csrc/cnn_policy.hip select_action of the pixel agent's conv net (f32 MFMAs as implicit GEMMs, the reference's
+                    per-env BatchNorm statistics) on be_observe_pixels' image (be_cnn_act); its host
+                    half without HIP -- the packed image's layout and index function, the argument checks --
+                    is csrc/cnn_host.h (CPU-tested)
 """
 from __future__ import annotations
 
@@ -63,9 +67,9 @@ VGPR_MFMA = ["-mllvm", "-amdgpu-mfma-vgpr-form"]
 KARG_PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
 UNITS = {"ballenv.hip": [*VGPR_MFMA, *KARG_PRELOAD], "abi.hip": [], "policy.hip": ["-fno-slp-vectorize", *VGPR_MFMA],
          "features.hip": [], "pixels.hip": [], "board.hip": [], "a2c.hip": [], "a2c_grad.hip": [], "a2c_adam.hip": [],
-         "mlp_policy.hip": [], "mlp_grad.hip": []}
+         "mlp_policy.hip": [], "mlp_grad.hip": [], "cnn_policy.hip": []}
 HEADERS = [HDR, *(os.path.join(CSRC, h) for h in ("philox.h", "internal.h", "host_logic.h", "pool_layout.h", "policy_core.h", "blocks_core.h", "mlp_core.h", "diag.h",
-                                              "step_types.h", "optim_core.h", "pixels_host.h"))]
+                                              "step_types.h", "optim_core.h", "pixels_host.h", "cnn_host.h"))]
 
 
 def _stale(out, deps):

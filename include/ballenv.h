@@ -400,6 +400,70 @@ const char* be_mlp_rollout_kernel(const be_mlp* mlp);
 /* Bytes of the packed weight image (staged once per workgroup in LDS). */
 int64_t be_mlp_bytes(const be_mlp* mlp);
 
+/* ---- on-GPU select_action of the pixel agent (the conv net of examples/ball_cnn_reinforce.py) ----
+ * Replaces, for every env at once, the caller's per-step
+ *   probs = Policy()(extract_patch(state), quadrant)     examples/ball_cnn_reinforce.py:60-83
+ *   action ~ Categorical(probs); saved log_prob           ball_cnn_reinforce.py:85-95
+ * The network: conv1 (3 -> 16), conv2 (16 -> 32), conv3 (32 -> 32), each 5 x 5 stride 2 with
+ * BatchNorm and relu (maps 18 x 18, 7 x 7, 2 x 2), then head: Linear(132, num_actions) on the 128
+ * features (channel-major) and the goal's quadrant one-hot, softmax.  It has no value head.
+ * The reference never calls eval() and feeds one image at a time, so each BatchNorm normalises with the
+ * statistics of that env's own feature map: BE_CNN_NORM_SAMPLE.  BE_CNN_NORM_RUNNING uses the stored
+ * running statistics (Policy.eval()).
+ * The arithmetic is pinned (csrc/cnn_policy.hip and csrc/cnn_host.h have the k order of the chains):
+ *   x      = (float)v / 255.0f per image byte, one IEEE division: be_observe_pixels' out_f32 values
+ *   conv   = bias + sum w x: f32 fma chains on v_mfma_f32_16x16x4_f32, the bias in the chain's start.
+ *            conv1: one chain of 19 steps of 4 (ci, ky ascending with kx = 0..3 in a step, then the kx = 4
+ *            column; K 75 -> 76 with a zero weight).  conv2: one chain of 100 steps, step 25 cg + tap
+ *            taking the input channels 4 cg .. 4 cg + 3 at tap (ky, kx) = (tap / 5, tap % 5).  conv3: eight
+ *            chains, chain c the 25 steps of the channels 4 c .. 4 c + 3 in that tap order, chain 0
+ *            starting at the bias, conv = ((c0 + c1) + (c2 + c3)) + ((c4 + c5) + (c6 + c7))
+ *   SAMPLE   mean = (sum conv) / n, var = (sum (conv - mean)^2) / n, n = 324, 49, 4: two passes, biased.
+ *            A sum runs over P = 8, 4, 4 interleaved partial sums (partial j takes the positions j, j + P,
+ *            ... in order, from 0.0f), combined pairwise: ((s0 + s1) + (s2 + s3)) + ((s4 + s5) + (s6 + s7)),
+ *            so four equal values have exactly their value as their mean.
+ *            No atomics: an env's statistics are the same bits wherever it runs
+ *   RUNNING  mean and var are the stored running_mean and running_var
+ *   y      = relu(((conv - mean) * (1.0f / sqrtf(var + 1e-5f))) * gamma + beta): IEEE sqrt and
+ *            division, no fused multiply-add
+ *   z      = head [flatten(y3), one_hot(quadrant)] + b: four chains, chain s & 3 taking step s (the
+ *            inputs 4 s .. 4 s + 3) for s < 32, the one-hot's step on chain 0, chain 0 starting at
+ *            the bias, z = (c0 + c1) + (c2 + c3)
+ *   p, a, log_prob, u: as be_mlp_act's (max-subtracted softmax, the inverse-CDF draw on the Philox
+ *            uniform keyed by (seed; global env id, episode, ep_len, POLICY))
+ * An env's outputs depend on its image, quadrant, episode counters and the seed only: not on N, the
+ * workgroup or round that takes it, or whether the launch was captured.                          */
+typedef struct be_cnn be_cnn;
+#define BE_CNN_NORM_SAMPLE 0
+#define BE_CNN_NORM_RUNNING 1
+typedef struct be_cnn_weights {     /* DEVICE f32 arrays in torch state_dict layout                 */
+  const float *conv1_weight, *conv1_bias;                                   /* (16, 3, 5, 5), (16)  */
+  const float *bn1_weight, *bn1_bias, *bn1_running_mean, *bn1_running_var;  /* (16) each            */
+  const float *conv2_weight, *conv2_bias;                                   /* (32, 16, 5, 5), (32) */
+  const float *bn2_weight, *bn2_bias, *bn2_running_mean, *bn2_running_var;  /* (32) each            */
+  const float *conv3_weight, *conv3_bias;                                   /* (32, 32, 5, 5), (32) */
+  const float *bn3_weight, *bn3_bias, *bn3_running_mean, *bn3_running_var;  /* (32) each            */
+  const float *head_weight, *head_bias;                                     /* (A, 132), (A)        */
+} be_cnn_weights;
+/* num_actions in [1, 15]. */
+int be_cnn_create(be_ctx* ctx, int32_t num_actions, be_cnn** out);
+int be_cnn_destroy(be_cnn* cnn);
+/* (Re)load the weights: one packing kernel into the image be_cnn_act reads (MFMA A fragments, K padded
+ * with zero weights, head rows padded to 16).  Every pointer is required and 4-byte aligned.
+ * Asynchronous on stream, graph-capturable, allocates nothing.                                    */
+int be_cnn_load(be_cnn* cnn, const be_cnn_weights* w, void* stream);
+/* select_action for every env of st.  image: the (N, 3, 40, 40) u8 image be_observe_pixels writes
+ * (required, 16-byte aligned).  quadrant_in NULL: the goal's quadrant is computed from st in the kernel
+ * (prep_state2's rule, be_observe_blocks' first four bytes); else N bytes in 0..3.  norm: BE_CNN_NORM_*.
+ * out->action is required, out->log_prob and out->probs (N, A) are optional, out->value must be NULL.
+ * A failed check is BE_E_INVALID with the argument named in be_last_error, and launches nothing; a
+ * handle never loaded is rejected.  st is not changed.  One launch, asynchronous on stream,
+ * graph-capturable, allocates nothing.                                                            */
+int be_cnn_act(be_cnn* cnn, const be_state* st, const uint8_t* image, const uint8_t* quadrant_in, int32_t norm,
+               const be_act_out* out, uint64_t seed, void* stream);
+/* Bytes of the packed weight image. */
+int64_t be_cnn_bytes(const be_cnn* cnn);
+
 /* ---- the block-count MLP's losses and gradients: both of the reference's training loops ----
  *   finish_episode       examples/ball_env_reinforce.py:88-108  sum of -Categorical(probs).log_prob(a) * R^
  *   the supervised loop  examples/train_supervise.py:66-101     mean CrossEntropyLoss on the logits
