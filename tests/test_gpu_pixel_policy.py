@@ -5,6 +5,8 @@ policy (examples/ball_cnn_reinforce.py:60-95) run in plain PyTorch fp32 on the C
 Floating point, so a tolerance -- the rule of tests/test_gpu_block_policy.py, taken over as it stands:
 * probs, log_prob: |hip - torch32| <= 2e-5 (abs), and the HIP error against an fp64 evaluation of the
   same weights is at most 4x torch fp32's own error + 1e-6;
+* the centred logits z = log p - mean log p, which a saturated softmax cannot hide:
+  |z_hip - z64| <= 4 |z_t32 - z64| + 8 * 2**-23 * (1 + max|z64|) (pixel_policy_cases.logit_bound);
 * action: identical to the inverse-CDF draw on the torch probs with the same Philox uniform
   (oracle.policy_uniforms), except where that uniform lies within 1e-5 of a CDF boundary; those
   cases are counted and capped at max(4, N // 1000).
@@ -17,8 +19,9 @@ import numpy as np
 import pytest
 import torch
 
-import helpers
 from oracle import oracle
+from pixel_policy_cases import (ACTION_COUNTS, ACTION_N, ACTION_SEED, CALIBRATED_SHAPES, CASES, RANDOM_SHAPES, Case, case_inputs,
+                                centred_logits, given_images, logit_bound, random_policy, reference, trained_policy)
 
 pytestmark = pytest.mark.gpu
 
@@ -32,45 +35,6 @@ def make(dev, N, seed=0x1234, W=10, time_limit=1000):
     return env
 
 
-def trained_policy():
-    from gym_ballenv_amd.pixel_policy import PixelPolicy, reference_pixel_weights
-    pol = PixelPolicy()
-    pol.load_state_dict(reference_pixel_weights(), strict=True)
-    return pol
-
-
-def random_policy(seed, A=9):
-    """conv and head parameters x3, gamma in [0.5, 1.5], beta in +-0.5, running mean in +-0.3, var in [0.2, 2]."""
-    from gym_ballenv_amd.pixel_policy import PixelPolicy
-    torch.manual_seed(seed)
-    pol = PixelPolicy(A)
-    with torch.no_grad():
-        for m in (pol.conv1, pol.conv2, pol.conv3, pol.head):
-            m.weight.mul_(3.0)
-            m.bias.mul_(3.0)
-        for bn in (pol.bn1, pol.bn2, pol.bn3):
-            bn.weight.uniform_(0.5, 1.5)
-            bn.bias.uniform_(-0.5, 0.5)
-            bn.running_mean.uniform_(-0.3, 0.3)
-            bn.running_var.uniform_(0.2, 2.0)
-    return pol
-
-
-def given_images(N, seed):
-    """(N, 3, 40, 40) u8 and (N,) u8 quadrants: all-white, all-black, white with one black pixel, noise, the
-    16 fixture images, more noise -- cycled from an offset of `seed`, so N = 1 takes another one per seed."""
-    g = torch.Generator().manual_seed(100 + seed)
-    white = torch.full((3, 40, 40), 255, dtype=torch.uint8)
-    dot = white.clone()
-    dot[:, 17, 22] = 0
-    pool = [white, torch.zeros(3, 40, 40, dtype=torch.uint8), dot]
-    pool += [torch.randint(0, 256, (3, 40, 40), generator=g, dtype=torch.uint8) for _ in range(2)]
-    pool += list(torch.from_numpy(helpers.load("pixels")["images"]))
-    pool += [torch.randint(0, 256, (3, 40, 40), generator=g, dtype=torch.uint8) for _ in range(9)]
-    img = torch.stack([pool[(i + seed) % len(pool)] for i in range(N)])
-    return img.contiguous(), (torch.arange(N) % 4).to(torch.uint8)
-
-
 def uniforms(env, seed):
     ep = env.episode.cpu().numpy().view(np.uint32)
     return torch.from_numpy(oracle.policy_uniforms(env._abi_cfg, ep, env.ep_len.cpu().numpy(), seed))
@@ -80,21 +44,13 @@ def env_quadrant(env):
     return env.observe_blocks()[:, :4].argmax(1).to(torch.uint8)
 
 
-def reference(pol, img, quad, u, norm):
-    """(action, log_prob, probs) of torch fp32 and the fp64 probs, on the CPU."""
-    from gym_ballenv_amd.pixel_policy import torch_pixel_forward, torch_pixel_select_action
-    with torch.no_grad():
-        ra, rlp, rpr = torch_pixel_select_action(pol.float(), img, quad, u, norm)
-        pr64 = torch_pixel_forward(pol.double(), img.double() / 255.0, torch.eye(4, dtype=torch.float64)[quad.long()], norm)
-        pol.float()
-    return ra, rlp, rpr, pr64
-
-
 def near_boundary(rpr, u):
     return ((rpr.cumsum(-1) - u.unsqueeze(-1)).abs() < 1e-5).any(-1)
 
 
-def check(got, ref, u):
+def check(got, ref, u, masked=False):
+    """masked: whether the fp64 reference may have probabilities below 1e-30, which the logit comparison leaves
+    out (the trained weights; never a random or calibrated policy)."""
     a, lp, pr = (x.cpu() for x in got)
     ra, rlp, rpr, pr64 = ref
     err_hip = (pr.double() - pr64).abs().max().item()
@@ -106,21 +62,32 @@ def check(got, ref, u):
     dlp = (lp[ok] - rlp[ok]).abs().max().item()
     print(f"|probs - t32| {d:.3g}  |log_prob - t32| {dlp:.3g}  err_hip {err_hip:.3g}  err_t32 {err_t32:.3g}  "
           f"near {int(near.sum())}  mismatches {int(mism.sum())} of {a.shape[0]}")
+    # the centred logits log p - mean log p of the f32 probabilities, the log taken in fp64: the bound is from the
+    # two references alone (pixel_policy_cases.logit_bound)
+    z64, mask = centred_logits(pr64)
+    z32, _ = centred_logits(rpr.double(), mask)
+    zhip, _ = centred_logits(pr.double(), mask)
+    bound = logit_bound(z64, z32)
+    zerr_hip, zerr_t32 = (zhip - z64).abs().max().item(), (z32 - z64).abs().max().item()
+    print(f"logits: err_hip {zerr_hip:.3g}  err_t32 {zerr_t32:.3g}  logit_bound {bound:.3g}  max|z| {z64.abs().max().item():.3g}  "
+          f"min p {pr64.min().item():.3g}  masked {int(mask.sum())} of {mask.numel()}")
     assert torch.isfinite(pr).all()
     assert d <= TOL
     assert err_hip <= 4 * err_t32 + 1e-6, (err_hip, err_t32)
+    assert int(mask.sum()) <= (mask.numel() // 100 if masked else 0)
+    assert zerr_hip <= bound, (zerr_hip, zerr_t32, bound)
     assert not (mism & ~near).any(), f"{int((mism & ~near).sum())} action mismatches away from CDF boundaries"
     assert int(near.sum()) <= max(4, a.shape[0] // 1000)
     assert dlp <= TOL
 
 
-def check_env(env, pol, hp, seed, img=None, quad=None):
+def check_env(env, pol, hp, seed, img=None, quad=None, masked=False):
     """act() on the env's state (img = quad = None) or on given inputs, against torch on the same inputs."""
     src = env.observe_pixels() if img is None else img
     q = env_quadrant(env) if quad is None else quad
     got = [x.clone() for x in hp.act(img, quad, seed=seed)]
     u = uniforms(env, seed)
-    check(got, reference(pol, src.cpu(), q.cpu(), u, hp.norm), u)
+    check(got, reference(pol, src.cpu(), q.cpu(), u, hp.norm), u, masked)
     return got
 
 
@@ -138,30 +105,120 @@ def test_trained_weights_on_env_states(gpu):
         _, _, done, _ = env.step(acts[t])
         resets += int(done.sum())
         if t in (19, 39):
-            got = check_env(env, pol, hp, seed=77 + t)
+            got = check_env(env, pol, hp, seed=77 + t, masked=True)
             assert got[2].max().item() < 1.0 and got[2].min().item() > 0.0
     assert resets >= N                                   # every env was reset by the time limit
     env.status()
     hp.close(); env.close()
 
 
-CASES = [(1, 9), (15, 15), (16, 1), (16, 9), (17, 9), (67, 15), (67, 9)]
-
-
 @pytest.mark.parametrize("norm", ["sample", "running"])
 @pytest.mark.parametrize("seed", [0, 1])
-@pytest.mark.parametrize("N,A", CASES)
+@pytest.mark.parametrize("N,A", RANDOM_SHAPES)
 def test_random_weights_given_images(gpu, N, A, seed, norm):
     """Random weights on the fixture images, noise, constant images (every map constant: variance 0, the eps
     path) and a single black pixel; quadrant_in covers 0..3; N on both sides of a tile and of a wave's share,
-    both ends of the action bound."""
+    both ends of the action bound.  In "running" mode these are the large-logit cases (probabilities down to
+    1e-11); half the channels of conv2 and conv3 are dead there, which the calibrated cases make up for."""
     from gym_ballenv_amd.pixel_policy import HipPixelPolicy
+    case = Case("random", norm, N, A, seed)
+    assert case in CASES
     env = make(gpu, N, W=3)
-    pol = random_policy(seed, A)
+    pol, img, quad = case_inputs(case)
     hp = HipPixelPolicy(env, pol, norm=norm, probs=True)
-    img, quad = given_images(N, seed)
     check_env(env, pol, hp, seed=5 + seed, img=img.to(gpu), quad=quad.to(gpu))
     hp.close(); env.close()
+
+
+@pytest.mark.parametrize("seed", [0, 1])
+@pytest.mark.parametrize("N,A", CALIBRATED_SHAPES)
+def test_calibrated_weights_given_images(gpu, N, A, seed):
+    """"running" mode with the running statistics a real eval-mode net has: each layer's pooled statistics over
+    the test's images.  Every channel is then alive on some image, and this is the mode in which the conv
+    biases matter: tests/test_pixel_policy_coverage_host.py shows that these cases see the whole packed image."""
+    from gym_ballenv_amd.pixel_policy import HipPixelPolicy
+    case = Case("calibrated", "running", N, A, seed)
+    assert case in CASES
+    env = make(gpu, N, W=3)
+    pol, img, quad = case_inputs(case)
+    hp = HipPixelPolicy(env, pol, norm="running", probs=True)
+    check_env(env, pol, hp, seed=5 + seed, img=img.to(gpu), quad=quad.to(gpu))
+    hp.close(); env.close()
+
+
+@pytest.mark.parametrize("A", ACTION_COUNTS)
+def test_every_action_count(gpu, A):
+    """One full tile and a partial one for every number of -inf pad rows of the head: probs, logits and the
+    draw against torch; a single action has probability exactly 1."""
+    from gym_ballenv_amd.pixel_policy import HipPixelPolicy
+    case = Case("actions", "sample", ACTION_N, A, ACTION_SEED)
+    assert case in CASES
+    env = make(gpu, ACTION_N, W=3)
+    pol, img, quad = case_inputs(case)
+    hp = HipPixelPolicy(env, pol, norm="sample", probs=True)
+    a, lp, pr = check_env(env, pol, hp, seed=40 + A, img=img.to(gpu), quad=quad.to(gpu))
+    assert pr.shape == (ACTION_N, A) and int(a.max()) < A
+    if A == 1:
+        assert bool((pr == 1.0).all()) and bool((a == 0).all()) and bool((lp == 0.0).all())
+    hp.close(); env.close()
+
+
+# goal - agent for 16 envs: dx in {< 0, 0, 0, > 0} crossed with dy in {< 0, 0, 0, > 0}, so each zero meets every
+# sign of the other coordinate; and blocks_init's rule dx >= 0 ? (dy >= 0 ? 1 : 2) : (dy >= 0 ? 0 : 3) by hand
+CUT_DX = [-7, -7, -7, -7, 0, 0, 0, 0, 0, 0, 0, 0, 5, 5, 5, 5]
+CUT_DY = [-3, 0, 0, 9] * 4
+CUT_QUADRANT = [3, 0, 0, 0, 2, 1, 1, 1, 2, 1, 1, 1, 2, 1, 1, 1]
+
+
+def test_quadrant_from_the_state_at_its_cuts(gpu):
+    """The kernel restates blocks_init's quadrant rule inline: with quadrant=None it must give what it gives on
+    be_observe_blocks' quadrant and on the rule written out by hand, bit for bit, where dx or dy is 0."""
+    from gym_ballenv_amd.pixel_policy import HipPixelPolicy
+    N = 16
+    env = make(gpu, N)
+    state = {k: v.clone() for k, v in env.state_dict().items()}
+    agent = torch.tensor([[200 + 9 * i, 150 + 5 * i] for i in range(N)], dtype=state["agent"].dtype)
+    delta = torch.tensor(list(zip(CUT_DX, CUT_DY)), dtype=state["agent"].dtype)
+    assert tuple(state["agent"].shape) == (N, 2) and tuple(state["goal"].shape) == (N, 2)
+    state["agent"], state["goal"] = agent, agent + delta
+    env.load_state_dict(state)
+    assert torch.equal(env.goal.cpu() - env.agent.cpu(), delta)
+    by_hand = torch.tensor(CUT_QUADRANT, dtype=torch.uint8, device=gpu)
+    assert torch.equal(env_quadrant(env), by_hand) and set(CUT_QUADRANT) == {0, 1, 2, 3}
+    pol = random_policy(3)
+    for norm in ("sample", "running"):
+        hp = HipPixelPolicy(env, pol, norm=norm, probs=True)
+        own = check_env(env, pol, hp, seed=12)
+        for q in (env_quadrant(env), by_hand):
+            for x, y in zip(own, hp.act(quadrant=q, seed=12)):
+                assert torch.equal(x, y)
+        other = hp.act(quadrant=(by_hand + 1) % 4, seed=12)[2]
+        assert bool((other != own[2]).any(1).all())         # the head's quadrant columns matter in every row
+        hp.close()
+    env.status()
+    env.close()
+
+
+def test_env_offset_keys_the_draw(gpu):
+    """The draw's Philox key is the global env id env_offset + e (past 16 bits here); nothing else depends on it."""
+    import gym_ballenv_amd as gb
+    from gym_ballenv_amd.pixel_policy import HipPixelPolicy
+    N, seed = 70, 17
+    pol = random_policy(5)
+    img, quad = given_images(N, 2)
+    outs = []
+    for offset in (0, 70000):
+        env = gb.BatchedBallEnv(N, 3, gb.EnvConfig(time_limit=1000), device=gpu, seed=0x1234, env_offset=offset)
+        env.reset()
+        assert env._abi_cfg.env_offset == offset
+        hp = HipPixelPolicy(env, pol, norm="sample", probs=True)
+        outs.append(check_env(env, pol, hp, seed=seed, img=img.to(gpu), quad=quad.to(gpu)))
+        outs[-1].append(uniforms(env, seed))
+        env.status()
+        hp.close(); env.close()
+    assert torch.equal(outs[0][2], outs[1][2])
+    assert not torch.equal(outs[0][3], outs[1][3])
+    assert not torch.equal(outs[0][0], outs[1][0])
 
 
 def test_position_independence(gpu):
