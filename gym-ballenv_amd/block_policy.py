@@ -25,11 +25,12 @@ weight image (``be_mlp_opt``); ``BlockTrainer`` and ``SupervisedTrainer`` are th
 host round trip, replayable as HIP graphs.
 ``torch_block_select_action`` is the same computation in plain PyTorch fp32 -- the numerics
 reference of the tests.
+What these classes share with the other two policies lives in their bases: ``_bind.HipHandle`` (the handle),
+``rollout.StepRollout`` (the T-step loop), ``optim.RowGrad`` (the gradient binding) and ``optim.HipOptim``.
 """
 from __future__ import annotations
 
 import ctypes as C
-import os
 from typing import Optional
 
 import numpy as np
@@ -38,8 +39,9 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _abi
-from .optim import HipOptim, is_f32
-from .rollout import GraphLoop, RolloutTrainer, a2c_targets, capture_steps
+from ._bind import HipHandle, categorical_pick, golden, want
+from .optim import HipOptim, RowGrad
+from .rollout import GraphLoop, RolloutTrainer, StepRollout, a2c_targets, discounted, episode_ids
 
 BLOCKS = 29                      # prep_state2's row: 4 quadrant + 5 x 5 blocks
 # be_mlp_act's work split (csrc/mlp_policy.hip): a persistent grid of one workgroup per compute unit,
@@ -50,6 +52,11 @@ TILE, WAVES = 16, 8
 # workgroup t % G, round t // G)
 GRAD_TILE, GRAD_WAVES, GRAD_MAX_SLOTS = 64, 4, 1024
 _KINDS = ("supervised3", "reinforce2")
+
+
+def _names(layers: int) -> list:
+    """The parameters of a BlockPolicy of this many layers, in the C structs' order."""
+    return [f"affine{i + 1}.{w}" for i in range(layers) for w in ("weight", "bias")]
 
 
 class BlockPolicy(nn.Module):
@@ -101,9 +108,7 @@ def reference_block_weights(kind: str) -> Optional[str]:
     ("supervised3": 3 layers, no final relu; "reinforce2": 2 layers), if present."""
     if kind not in _KINDS:
         raise ValueError(f"kind must be one of {_KINDS}")
-    p = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(__file__))), "tests", "golden",
-                     f"block_policy_{kind}.npz")
-    return p if os.path.exists(p) else None
+    return golden(f"block_policy_{kind}.npz")
 
 
 def torch_block_select_action(policy: BlockPolicy, blocks: torch.Tensor, u: torch.Tensor):
@@ -111,15 +116,10 @@ def torch_block_select_action(policy: BlockPolicy, blocks: torch.Tensor, u: torc
     ``a = #{j : cdf_j <= u}`` (clamped to the last action with p > 0) from given uniforms ``u`` (N,)
     -- the rule the HIP kernel uses.  Returns (action int64, log_prob, probs)."""
     probs = policy(blocks.float())
-    cdf = probs.cumsum(-1)
-    a = (cdf <= u.unsqueeze(-1)).sum(-1)
-    nz = torch.arange(probs.shape[-1], device=probs.device).expand_as(probs).masked_fill(probs <= 0, 0)
-    a = torch.minimum(a, nz.max(-1).values)
-    logp = torch.log(probs.gather(-1, a.unsqueeze(-1))).squeeze(-1)
-    return a, logp, probs
+    return (*categorical_pick(probs, u), probs)
 
 
-class HipBlockPolicy:
+class HipBlockPolicy(HipHandle):
     """``be_mlp_act`` bound to one BatchedBallEnv.
 
     ``load(policy)`` packs the module's current fp32 weights on the device (one small kernel,
@@ -127,22 +127,13 @@ class HipBlockPolicy:
     ``action`` (N,) u8, ``log_prob`` (N,) f32 and, if ``probs=True``, ``probs`` (N, A) f32.
     """
 
-    def __init__(self, env, policy: BlockPolicy, probs: bool = False, seed: int = 0x5E1EC7):
-        self.env = env
-        self._lib = _abi.lib()
+    ENTRIES = ("be_mlp_create", "be_mlp_destroy", "be_mlp_bytes")
+
+    def __init__(self, env, policy: BlockPolicy, probs: bool = False, seed: Optional[int] = None):
         self.layers, self.hidden1, self.hidden2 = policy.layers, policy.hidden1, policy.hidden2
-        self.num_actions, self.final_relu, self.seed = policy.num_actions, policy.final_relu, int(seed)
-        dev, N = env.device, env.num_envs
-        self.action = torch.zeros(N, dtype=torch.uint8, device=dev)
-        self.log_prob = torch.zeros(N, dtype=torch.float32, device=dev)
-        self.probs = torch.zeros(N, self.num_actions, dtype=torch.float32, device=dev) if probs else None
-        self._out = _abi.BeActOut(self.action.data_ptr(), self.log_prob.data_ptr(), None,
-                                  None if self.probs is None else self.probs.data_ptr())
-        h = C.c_void_p()
-        _abi.check(self._lib.be_mlp_create(env._ctx, self.layers, self.hidden1, self.hidden2, self.num_actions,
-                                           int(self.final_relu), C.byref(h)), env._ctx)
-        self._h = h
-        self._weights = None
+        self.final_relu = policy.final_relu
+        super().__init__(env, (self.layers, self.hidden1, self.hidden2, policy.num_actions, int(self.final_relu)),
+                         policy.num_actions, probs, seed)
         self.load(policy)
 
     def load(self, policy: BlockPolicy) -> None:
@@ -159,20 +150,11 @@ class HipBlockPolicy:
         self._weights = ws          # keep alive until the packing kernel has run
 
     @property
-    def packed_bytes(self) -> int:
-        return int(self._lib.be_mlp_bytes(self._h))
-
-    @property
     def rollout_kernel(self) -> Optional[str]:
         """The fused kernel instance ``be_mlp_rollout`` launches for this env and network
         (``be_mlp_rollout_kernel``), or None where it loops ``be_mlp_act`` + ``be_step``."""
         r = self._lib.be_mlp_rollout_kernel(self._h)
         return r.decode() if r else None
-
-    def _check_rows(self, x: torch.Tensor, name: str) -> None:
-        if x.dtype != torch.uint8 or tuple(x.shape) != (self.env.num_envs, BLOCKS) or not x.is_contiguous() or \
-                x.device != self.env.device:
-            raise ValueError(f"{name} must be an (N, 29) contiguous u8 tensor on the env's device")
 
     def act(self, blocks: Optional[torch.Tensor] = None, record: Optional[torch.Tensor] = None,
             seed: Optional[int] = None):
@@ -180,36 +162,21 @@ class HipBlockPolicy:
         ``prep_state2`` of the env's current state, computed in the kernel); record: an (N, 29) u8
         tensor that receives the rows ``env.observe_blocks()`` would return.
         Returns (action, log_prob, probs)."""
-        if blocks is not None:
-            self._check_rows(blocks, "blocks")
-        if record is not None:
-            self._check_rows(record, "record")
-        s = self.seed if seed is None else int(seed)
-        _abi.check(self._lib.be_mlp_act(self._h, C.byref(self.env._st), None if blocks is None else blocks.data_ptr(),
+        env = self.env
+        want(blocks, "blocks", torch.uint8, (env.num_envs, BLOCKS), env.device, optional=True)
+        want(record, "record", torch.uint8, (env.num_envs, BLOCKS), env.device, optional=True)
+        _abi.check(self._lib.be_mlp_act(self._h, C.byref(env._st), None if blocks is None else blocks.data_ptr(),
                                         None if record is None else record.data_ptr(), C.byref(self._out),
-                                        s & (2**64 - 1), self.env._stream()), self.env._ctx)
+                                        self._seed(seed), env._stream()), env._ctx)
         return self.action, self.log_prob, self.probs
 
-    def close(self) -> None:
-        if getattr(self, "_h", None) is not None:
-            torch.cuda.synchronize(self.env.device)
-            self._lib.be_mlp_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class BlockRollout:
+class BlockRollout(StepRollout):
     """T steps of every env with the block policy in the loop (ball_env_reinforce.py's episode loop,
     batched): per step ``be_mlp_act`` writes action and log_prob into row t (and, with ``record_obs``,
     the block counts the action was drawn from into row t of ``blocks`` (T, N, 29) u8), then ``be_step``
-    writes rewards and dones into row t.  The per-step out-structs point into the (T, N) buffers, so
-    there are no copy kernels; ``capture()`` records the loop into HIP graphs (a linear chain on one
-    stream) and ``run()`` replays them.
+    writes rewards and dones into row t.  The loop, its (T, N) buffers, ``capture()`` and ``run()`` are
+    ``StepRollout``'s (rollout.py).
 
     ``backend="fused"`` runs the same T steps as ``be_mlp_rollout`` launches of ``chunk`` steps each into the
     same buffers: the policy and the env step in one kernel, each env's state in registers and the packed
@@ -220,100 +187,33 @@ class BlockRollout:
                  backend: str = "hip", chunk: int = 100):
         if backend not in ("hip", "fused"):
             raise ValueError("backend must be 'hip' or 'fused'")
-        self.env, self.policy, self.T, self.seed = env, policy, int(horizon), int(seed)
-        self.backend, self.chunk = backend, max(1, int(chunk))
-        dev, N, T = env.device, env.num_envs, self.T
-        self.actions = torch.zeros(T, N, dtype=torch.uint8, device=dev)
-        self.log_probs = torch.zeros(T, N, dtype=torch.float32, device=dev)
-        self.rewards = torch.zeros(T, N, dtype=torch.float64, device=dev)
-        self.dones = torch.zeros(T, N, dtype=torch.bool, device=dev)
-        self.blocks = torch.zeros(T, N, BLOCKS, dtype=torch.uint8, device=dev) if record_obs else None
-        self.hp = HipBlockPolicy(env, policy, seed=self.seed)
-        self._lib = _abi.lib()
-        self._graphs = []
-        self._act_outs = [_abi.BeActOut(self.actions[t].data_ptr(), self.log_probs[t].data_ptr(), None, None)
-                          for t in range(T)]
-        o = env._out
-        self._step_outs = [_abi.BeOut(o.obs, o.obs_f32, self.rewards[t].data_ptr(), self.dones[t].data_ptr(),
-                                      o.truncated, o.terminal_obs, o.final_return, o.final_len, o.stats)
-                           for t in range(T)]
+        super().__init__(env, policy, HipBlockPolicy(env, policy, seed=int(seed)), horizon, seed, backend, chunk)
+        self.blocks = torch.zeros(self.T, env.num_envs, BLOCKS, dtype=torch.uint8, device=env.device) \
+            if record_obs else None
 
-    def run_fused(self, stream_ptr=None) -> None:
-        """The horizon as be_mlp_rollout launches of ``chunk`` steps (backend="fused")."""
-        env, lib = self.env, self._lib
-        s = env._stream() if stream_ptr is None else stream_ptr
-        for c0 in range(0, self.T, self.chunk):
-            k = min(self.chunk, self.T - c0)
-            out = _abi.BeOut(None, None, self.rewards[c0].data_ptr(), self.dones[c0].data_ptr(), None, None,
-                             None, None, env._out.stats)
-            act = _abi.BeActOut(self.actions[c0].data_ptr(), self.log_probs[c0].data_ptr(), None, None)
-            rec = None if self.blocks is None else self.blocks[c0].data_ptr()
-            rc = lib.be_mlp_rollout(self.hp._h, C.byref(env._st), env.obs.data_ptr(), rec, k, C.byref(out),
-                                    C.byref(act), self.seed & (2**64 - 1), s)
-            if rc:
-                _abi.check(rc, env._ctx)
+    def _launch(self, c0: int, k: int, act, s) -> int:
+        env = self.env
+        out = self._chunk_out(c0, None)
+        rec = None if self.blocks is None else self.blocks[c0].data_ptr()
+        return self._lib.be_mlp_rollout(self.hp._h, C.byref(env._st), env.obs.data_ptr(), rec, k, C.byref(out),
+                                        C.byref(act), self.seed & (2**64 - 1), s)
 
-    def step(self, t: int, stream_ptr=None) -> None:
-        """select_action + env step of every env, results into row t."""
-        if self.backend == "fused":
-            raise RuntimeError("backend='fused' has no single step: run() / run_eager() issue be_mlp_rollout launches")
-        env, lib = self.env, self._lib
-        s = env._stream() if stream_ptr is None else stream_ptr
+    def _act(self, t: int, s) -> None:
+        env = self.env
         rec = None if self.blocks is None else self.blocks[t].data_ptr()
-        rc = lib.be_mlp_act(self.hp._h, C.byref(env._st), None, rec, C.byref(self._act_outs[t]),
-                            self.seed & (2**64 - 1), s)
+        rc = self._lib.be_mlp_act(self.hp._h, C.byref(env._st), None, rec, C.byref(self._act_outs[t]),
+                                  self.seed & (2**64 - 1), s)
         if rc:
             _abi.check(rc, env._ctx)
-        rc = lib.be_step(env._ctx, C.byref(env._st), C.c_void_p(self.actions[t].data_ptr()), None, None,
-                         C.byref(self._step_outs[t]), s)
-        if rc:
-            _abi.check(rc, env._ctx)
-
-    def run_eager(self) -> None:
-        if self.backend == "fused":
-            return self.run_fused()
-        for t in range(self.T):
-            self.step(t)
-
-    def capture(self, chunk: int = 250, stream: Optional[torch.cuda.Stream] = None) -> None:
-        """Record the T steps into HIP graphs of ``chunk`` steps each (stream: the stream to capture
-        on; default a new one from torch's pool)."""
-        if self.backend == "fused":     # a few launches per horizon: nothing to capture
-            self._graphs = []
-            return
-        self._graphs = capture_steps(self.step, self.T, chunk, self.env.device, stream)
-
-    def run(self) -> None:
-        """Replay the captured horizon (capture() first)."""
-        if self.backend == "fused":
-            return self.run_fused()
-        if not self._graphs:
-            raise RuntimeError("capture() first")
-        for g in self._graphs:
-            g.replay()
-
-    def close(self) -> None:
-        self._graphs = []
-        self.hp.close()
 
 
 def _episode_targets(rewards: torch.Tensor, dones: torch.Tensor, gamma: float, eps: float):
     """(R^, valid), flat (T*N), by be_a2c_targets' rule in plain torch: the return recursion in f64,
     R rounded to fp32 (the reference's torch.tensor(R)), then each episode's mean and unbiased std of
     those fp32 values taken in f64 and R^ rounded once to fp32."""
-    T, N = rewards.shape
     dev = rewards.device
-    d64 = dones.to(torch.float64)
-    R = torch.empty(T, N, dtype=torch.float64, device=dev)
-    acc = torch.zeros(N, dtype=torch.float64, device=dev)
-    for t in range(T - 1, -1, -1):
-        acc = rewards[t].to(torch.float64) + gamma * acc * (1.0 - d64[t])
-        R[t] = acc
-    flat = R.to(torch.float32).to(torch.float64).reshape(-1)
-    # episode id of every (t, env): dones strictly before t in that env, then env
-    seg = (torch.cumsum(dones.to(torch.int64), 0) - dones.to(torch.int64)) * N + torch.arange(N, device=dev)
-    _, sid = torch.unique(seg.reshape(-1), return_inverse=True)
-    S = int(sid.max()) + 1
+    flat = discounted(rewards, dones, gamma).to(torch.float32).to(torch.float64).reshape(-1)
+    sid, S = episode_ids(dones)
     cnt = torch.bincount(sid, minlength=S).to(torch.float64)
     mean = torch.zeros(S, dtype=torch.float64, device=dev).index_add_(0, sid, flat) / cnt
     var = torch.zeros(S, dtype=torch.float64, device=dev).index_add_(0, sid, (flat - mean[sid]) ** 2) / \
@@ -351,91 +251,42 @@ def reinforce_losses(policy: BlockPolicy, blocks: torch.Tensor, actions: torch.T
     return -(logp.double() * Rn.double())[valid].sum()      # products and sum in f64: no rounding of its own
 
 
-class BlockGrad:
+class BlockGrad(RowGrad):
     """``be_mlp_grad`` bound to one BatchedBallEnv and one BlockPolicy: the loss sum of ``reinforce_losses``
     (loss="reinforce") or of ``supervised_losses`` (loss="xent", with scale = 1 / batch for its mean) and
-    what ``loss.backward()`` leaves in each ``.grad``, from the recorded u8 block counts in two
-    launches (include/ballenv.h pins the arithmetic; reproducible bit for bit).
-
-    Owns the workspace, the gradient tensors (``.grads``, keyed like ``policy.state_dict()``) and the
-    f64 pair ``.losses`` (scale * the sum of the row losses, the number of active rows); nothing is
-    allocated per call, so a call can be graph-captured.  The weights are read from the module's
-    parameters at call time (fp32, contiguous, on the env's device)."""
+    what ``loss.backward()`` leaves in each ``.grad``, from the recorded u8 block counts in two launches.
+    The workspace, the gradient tensors (``.grads``), the checks and ``assign()``: ``RowGrad`` (optim.py);
+    ``.losses`` is its f64 pair (scale * the sum of the row losses, the number of active rows)."""
 
     LOSSES = {"reinforce": _abi.MLP_LOSS_REINFORCE, "xent": _abi.MLP_LOSS_XENT}
+    LOSS_WIDTH = 2
+    WEIGHTS, GRADS = _abi.BeMlpWeights, _abi.BeMlpGrads
 
     def __init__(self, env, policy: BlockPolicy):
-        self.env, self.policy = env, policy
-        self._lib = _abi.lib()
-        dev = env.device
         self.layers, self.hidden1, self.hidden2 = policy.layers, policy.hidden1, policy.hidden2
         self.num_actions, self.final_relu = policy.num_actions, policy.final_relu
-        nbytes = int(self._lib.be_mlp_grad_workspace_bytes(env._ctx, self.layers, self.hidden1, self.hidden2,
-                                                           self.num_actions))
-        if nbytes < 0:
-            _abi.check(nbytes, env._ctx)
-        self.workspace = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
-        self._names = [f"affine{i + 1}.{w}" for i in range(self.layers) for w in ("weight", "bias")]
-        sd = policy.state_dict()
-        self.grads = {k: torch.zeros(sd[k].shape, dtype=torch.float32, device=dev) for k in self._names}
-        self.losses = torch.zeros(2, dtype=torch.float64, device=dev)
-        ptrs = [self.grads[k].data_ptr() for k in self._names] + [None] * (6 - len(self._names))
-        self._g = _abi.BeMlpGrads(*ptrs, self.losses.data_ptr())
-        self._weights = None
-
-    def _params(self):
-        ps = dict(self.policy.named_parameters())
-        ws = [ps[k].detach() for k in self._names]
-        for k, w in zip(self._names, ws):
-            if not is_f32(w, self.grads[k].shape, self.env.device):
-                raise ValueError(f"policy parameter {k} must be a contiguous f32 tensor of the shape BlockGrad was "
-                                 "made for, on the env's device")
-        return ws
+        sizes = (self.layers, self.hidden1, self.hidden2, self.num_actions)
+        super().__init__(env, policy, _names(self.layers), "be_mlp_grad_workspace_bytes", sizes,
+                         (*sizes, int(self.final_relu)))
+        self.losses = self._losses
 
     def __call__(self, blocks: torch.Tensor, actions: torch.Tensor, coef: Optional[torch.Tensor] = None,
                  valid: Optional[torch.Tensor] = None, loss: str = "reinforce", scale: float = 1.0):
         """blocks (T, N, 29) or (rows, 29) u8; actions u8 (the labels with loss="xent"), coef f32 or None
         (= 1), valid u8 / bool or None (= every row), each (T, N) or (rows,): contiguous, on the env's
         device.  Asynchronous on the caller's current stream.  Returns ``.grads``."""
-        dev = self.env.device
         if loss not in self.LOSSES:
             raise ValueError("loss must be 'reinforce' or 'xent'")
-        if blocks.dtype != torch.uint8 or blocks.dim() not in (2, 3) or blocks.shape[-1] != BLOCKS or \
-                not blocks.is_contiguous() or blocks.device != dev:
-            raise ValueError("blocks must be a (T, N, 29) or (rows, 29) contiguous u8 tensor on the env's device")
-        lead = tuple(blocks.shape[:-1])
-        if actions.dtype != torch.uint8 or tuple(actions.shape) != lead or not actions.is_contiguous() or \
-                actions.device != dev:
-            raise ValueError("actions must be a contiguous u8 tensor of blocks' leading shape on the env's device")
-        if coef is not None and (coef.dtype != torch.float32 or tuple(coef.shape) != lead or
-                                 not coef.is_contiguous() or coef.device != dev):
-            raise ValueError("coef must be a contiguous f32 tensor of blocks' leading shape on the env's device")
-        if valid is not None and (valid.dtype not in (torch.bool, torch.uint8) or tuple(valid.shape) != lead or
-                                  not valid.is_contiguous() or valid.device != dev):
-            raise ValueError("valid must be a contiguous bool / u8 tensor of blocks' leading shape on the env's device")
-        rows = 1
-        for n in lead:
-            rows *= int(n)
-        ws = self._params()
-        ptrs = [x.data_ptr() for x in ws] + [None] * (6 - len(ws))
-        w = _abi.BeMlpWeights(*ptrs, self.layers, self.hidden1, self.hidden2, self.num_actions, int(self.final_relu))
+        rows = self._rows(blocks, "blocks", BLOCKS,
+                          ((actions, "actions", torch.uint8, False), (coef, "coef", torch.float32, True),
+                           (valid, "valid", (torch.bool, torch.uint8), True)))
+        ws, w = self._params()
         rc = self._lib.be_mlp_grad(self.env._ctx, blocks.data_ptr(), actions.data_ptr(),
                                    None if coef is None else coef.data_ptr(),
                                    None if valid is None else valid.data_ptr(), rows, self.LOSSES[loss], float(scale),
                                    C.byref(w), self.workspace.data_ptr(), self.workspace.numel() * 8,
                                    C.byref(self._g), self.env._stream())
-        if rc:
-            _abi.check(rc, self.env._ctx)
-        self._weights = ws          # keep alive until the kernels have run
-        return self.grads
-
-    def assign(self) -> None:
-        """The gradients of the last call into the module's ``.grad`` (copies; stream-ordered)."""
-        for k, prm in self.policy.named_parameters():
-            if prm.grad is None:
-                prm.grad = self.grads[k].clone()
-            else:
-                prm.grad.copy_(self.grads[k])
+        return self._ran(rc, ws)
 
 
 class HipBlockOptim(HipOptim):
@@ -464,8 +315,7 @@ class HipBlockOptim(HipOptim):
         hp = hip_block_policy
         h1, h2, A = hp.hidden1, hp.hidden2, hp.num_actions
         shapes = [(h1, BLOCKS), (h1,)] + ([(h2, h1), (h2,), (A, h2), (A,)] if hp.layers == 3 else [(A, h1), (A,)])
-        names = [f"affine{i + 1}.{w}" for i in range(hp.layers) for w in ("weight", "bias")]
-        super().__init__(hp, policy, _abi.lib().be_mlp_opt, names, shapes, kind, lr, betas, eps, log_rows)
+        super().__init__(hp, policy, _abi.lib().be_mlp_opt, _names(hp.layers), shapes, kind, lr, betas, eps, log_rows)
 
 
 def _check_block_optim(optimizer, hp, policy) -> bool:
@@ -527,9 +377,7 @@ def reinforce_update(rollout: BlockRollout, optimizer, gamma: float = 0.99, targ
 def reference_supervise_data() -> Optional[str]:
     """Path of the committed fixture of the reference's supervised training data (one recorded trial:
     ``blocks`` (3186, 29) u8, ``labels`` (3186,) u8; tests/golden/make_supervise_fixture.py), if present."""
-    p = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(__file__))), "tests", "golden",
-                     "supervise_trial2.npz")
-    return p if os.path.exists(p) else None
+    return golden("supervise_trial2.npz")
 
 
 def supervised_losses(policy: BlockPolicy, blocks: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
@@ -615,13 +463,10 @@ class SupervisedTrainer(GraphLoop):
 
     def __init__(self, env, policy: BlockPolicy, blocks: torch.Tensor, labels: torch.Tensor, batch_size: int = 200,
                  lr: float = 1e-2, log_rows: int = 0):
-        dev = env.device
-        if blocks.dtype != torch.uint8 or blocks.dim() != 2 or blocks.shape[1] != BLOCKS or blocks.shape[0] < 1 or \
-                not blocks.is_contiguous() or blocks.device != dev:
-            raise ValueError("blocks must be a (rows, 29) contiguous u8 tensor on the env's device")
-        if labels.dtype != torch.uint8 or tuple(labels.shape) != (blocks.shape[0],) or not labels.is_contiguous() or \
-                labels.device != dev:
-            raise ValueError("labels must be a (rows,) contiguous u8 tensor on the env's device")
+        rows = int(want(blocks, "blocks", torch.uint8, (None, BLOCKS), env.device).shape[0])
+        want(labels, "labels", torch.uint8, (rows,), env.device)
+        if rows < 1:
+            raise ValueError("blocks must have at least one row")
         if int(batch_size) < 1:
             raise ValueError("batch_size must be >= 1")
         self.env, self.policy, self.blocks, self.labels = env, policy, blocks, labels
@@ -629,7 +474,6 @@ class SupervisedTrainer(GraphLoop):
         self.hp = self._closes = HipBlockPolicy(env, policy)
         self.grad = BlockGrad(env, policy)
         self.opt = HipBlockOptim(self.hp, policy, "sgd", lr=lr, log_rows=log_rows)
-        rows = int(blocks.shape[0])
         self._batches = [(blocks[i:j], labels[i:j], 1.0 / (j - i))
                          for i in range(0, rows, self.batch_size) for j in (min(rows, i + self.batch_size),)]
 

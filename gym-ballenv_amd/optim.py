@@ -1,27 +1,30 @@
-"""What the two on-GPU optimisers share: ``HipOptim``, the base of ``HipAdam`` (rollout.py: ``be_a2c_adam``
-on the six ``Policy`` tensors) and ``HipBlockOptim`` (block_policy.py: ``be_mlp_opt`` on the four or six
-``BlockPolicy`` tensors).  Both C entries take the same arguments behind their handle -- params, grads and
+"""What the on-GPU optimisers and gradient classes share.  ``HipOptim`` is the base of ``HipAdam`` (rollout.py:
+``be_a2c_adam`` on the six ``Policy`` tensors) and ``HipBlockOptim`` (block_policy.py: ``be_mlp_opt`` on the four
+or six ``BlockPolicy`` tensors).  Both C entries take the same arguments behind their handle -- params, grads and
 the two moments as tensor structs, the device state, the Adam constants, the losses and the loss log -- so
 everything but the names, shapes, struct and entry lives here: the tensor checks, ``step()`` up to the
 C call, the device state and learning rate, the loss-log ring and ``state_dict`` interchange with the torch
-optimisers.  Also the helpers of that surface other classes use: ``is_f32`` (the one weight check),
+optimisers.  ``RowGrad`` is the same for ``A2CGrad`` and ``BlockGrad`` (``be_a2c_grad``, ``be_mlp_grad``): the
+workspace, the gradient tensors, the checks of the weights and of the row tensors, and ``assign()``.  Also the
+helpers of that surface other classes use: ``is_f32`` (the weight check: ``_bind.fits`` for f32),
 ``unrolled_log`` and ``_beta_powers``.
 """
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Optional
 
 import torch
 
 from . import _abi
+from ._bind import fits, want
 
 
 def is_f32(x, shape, device) -> bool:
     """x is a contiguous f32 tensor of this shape (a tuple) on this device: what every kernel here reads
     its weights, gradients and moments as."""
-    return isinstance(x, torch.Tensor) and x.dtype == torch.float32 and x.is_contiguous() and \
-        x.device == device and tuple(x.shape) == shape
+    return fits(x, torch.float32, tuple(shape), device)
 
 
 def _beta_powers(t: int, betas):
@@ -117,8 +120,8 @@ class HipOptim:
             gs = [self._check("gradient of", k, grads[k]) for k in self._names]
         lp = gp = None
         if losses is not None and self.loss_log is not None:
-            if losses.dtype != torch.float64 or losses.numel() != self.LOSS_WIDTH or not losses.is_contiguous() or \
-                    losses.device != self.env.device:
+            if not fits(losses, torch.float64, (None,) * losses.dim(), self.env.device) or \
+                    losses.numel() != self.LOSS_WIDTH:
                 raise ValueError(f"losses must be {self.LOSS_WIDTH} contiguous f64 on the {self.ON}'s device")
             lp, gp = losses.data_ptr(), self.loss_log.data_ptr()
         w = self.STRUCT(*(x.data_ptr() for x in ws), *self._pad)
@@ -211,3 +214,67 @@ class HipOptim:
             float(grp["lr"])
         p1, p2 = _beta_powers(t, self.betas)
         self.state.copy_(torch.tensor([float(t), p1, p2, self._lr], dtype=torch.float64))
+
+
+class RowGrad:
+    """A loss and its gradients over recorded rows, in one asynchronous C entry bound to one BatchedBallEnv and
+    one policy module (include/ballenv.h pins the arithmetic; reproducible bit for bit).
+
+    Owns the workspace, the gradient tensors (``.grads``, keyed like ``policy.state_dict()``) and the
+    LOSS_WIDTH f64 ``_losses``; nothing is allocated per call, so a call can be graph-captured.  The weights
+    are read from the module's parameters at call time (fp32, contiguous, on the env's device).
+
+    A subclass says what differs, as data: LOSS_WIDTH, WEIGHTS and GRADS (the ctypes structs: six tensor
+    pointers, unused ones NULL, then the network's sizes resp. the losses), and to ``__init__`` the parameters'
+    names in the structs' order, the name of its ``*_workspace_bytes`` entry with that entry's sizes, and the
+    sizes that end WEIGHTS.  Its ``__call__`` checks its rows (``_rows``), makes the C call on ``_params()``
+    and ends in ``_ran``."""
+
+    LOSS_WIDTH = 0
+    WEIGHTS = GRADS = None
+
+    def __init__(self, env, policy, names, workspace_entry: str, workspace_sizes, sizes):
+        self.env, self.policy = env, policy
+        self._lib = _abi.lib()
+        dev = env.device
+        nbytes = int(getattr(self._lib, workspace_entry)(env._ctx, *workspace_sizes))
+        if nbytes < 0:
+            _abi.check(nbytes, env._ctx)
+        self.workspace = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+        self._names, self._sizes, self._pad = tuple(names), tuple(sizes), (None,) * (6 - len(names))
+        sd = policy.state_dict()
+        self.grads = {k: torch.zeros(sd[k].shape, dtype=torch.float32, device=dev) for k in self._names}
+        self._losses = torch.zeros(self.LOSS_WIDTH, dtype=torch.float64, device=dev)
+        self._g = self.GRADS(*(self.grads[k].data_ptr() for k in self._names), *self._pad, self._losses.data_ptr())
+        self._weights = None
+
+    def _params(self):
+        """The module's parameters, checked, and their WEIGHTS struct."""
+        ps, dev = dict(self.policy.named_parameters()), self.env.device
+        ws = [want(ps[k].detach(), f"policy parameter {k}", torch.float32, tuple(self.grads[k].shape), dev)
+              for k in self._names]
+        return ws, self.WEIGHTS(*(x.data_ptr() for x in ws), *self._pad, *self._sizes)
+
+    def _rows(self, x, name: str, width: int, others) -> int:
+        """Check the u8 rows ``x`` ((T, N, width) or (rows, width)) and ``others``, each (tensor, name, dtype,
+        optional) of x's leading shape; returns the number of rows."""
+        dev = self.env.device
+        lead = (None, None) if isinstance(x, torch.Tensor) and x.dim() == 3 else (None,)
+        lead = tuple(want(x, name, torch.uint8, (*lead, width), dev).shape[:-1])
+        for y, yname, dtype, optional in others:
+            want(y, yname, dtype, lead, dev, optional)
+        return math.prod(lead)
+
+    def _ran(self, rc: int, ws):
+        if rc:
+            _abi.check(rc, self.env._ctx)
+        self._weights = ws          # keep alive until the kernels have run
+        return self.grads
+
+    def assign(self) -> None:
+        """The gradients of the last call into the module's ``.grad`` (copies; stream-ordered)."""
+        for k, prm in self.policy.named_parameters():
+            if prm.grad is None:
+                prm.grad = self.grads[k].clone()
+            else:
+                prm.grad.copy_(self.grads[k])

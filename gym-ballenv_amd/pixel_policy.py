@@ -12,8 +12,9 @@ and the 4 quadrant inputs, softmax.  Its inputs come from the env's HIP observat
 ``HipPixelPolicy`` runs the reference's ``select_action`` (:85-95) for every env in one launch of the
 kernel in csrc/cnn_policy.hip (``be_cnn_act``) on the u8 image ``be_observe_pixels`` writes; ``PixelRollout``
 is the T-step loop ``observe_pixels -> be_cnn_act -> be_step`` into (T, N) buffers, capturable into HIP
-graphs.  The reference never calls ``policy.eval()`` and feeds one image at a time, so every BatchNorm
-layer normalises with the statistics of that env's own feature map: ``norm="sample"`` (the default of
+graphs.  The handle is a ``_bind.HipHandle`` and the loop ``rollout.StepRollout``'s: the two classes here add
+their own ``load()`` / ``act()`` and the policy half of a step.
+The reference never calls ``policy.eval()`` and feeds one image at a time, so every BatchNorm layer normalises with the statistics of that env's own feature map: ``norm="sample"`` (the default of
 the HIP path).  ``norm="running"`` uses the stored running statistics, as ``PixelPolicy.eval()`` does.
 ``torch_pixel_forward`` / ``torch_pixel_select_action`` are both modes in plain PyTorch -- the numerics
 reference of the tests.
@@ -21,7 +22,6 @@ reference of the tests.
 from __future__ import annotations
 
 import ctypes as C
-import os
 from typing import Optional
 
 import numpy as np
@@ -30,7 +30,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _abi
-from .rollout import capture_steps
+from ._bind import HipHandle, categorical_pick, golden, want
+from .rollout import StepRollout
 
 # be_cnn_act's work split (csrc/cnn_host.h): a persistent grid of one workgroup per compute unit, WAVES waves
 # each, a workgroup taking TILE envs per round (tile t of G workgroups: workgroup t % G, round t // G)
@@ -99,12 +100,7 @@ def torch_pixel_select_action(policy: PixelPolicy, image_u8: torch.Tensor, quadr
     x = image_u8.to(torch.float32) / 255.0
     q = F.one_hot(quadrant.long(), 4).to(torch.float32)
     probs = torch_pixel_forward(policy, x, q, norm)
-    cdf = probs.cumsum(-1)
-    a = (cdf <= u.unsqueeze(-1)).sum(-1)
-    nz = torch.arange(probs.shape[-1], device=probs.device).expand_as(probs).masked_fill(probs <= 0, 0)
-    a = torch.minimum(a, nz.max(-1).values)
-    logp = torch.log(probs.gather(-1, a.unsqueeze(-1))).squeeze(-1)
-    return a, logp, probs
+    return (*categorical_pick(probs, u), probs)
 
 
 def reference_pixel_weights() -> dict:
@@ -112,10 +108,9 @@ def reference_pixel_weights() -> dict:
     (examples/stored_models/cnn_train_models/episode_900.pth), from the two committed fixtures
     tests/golden/pixel_policy_cnn.npz and pixel_policy_cnn_conv3.npz (make_pixel_policy_fixture.py);
     ``PixelPolicy().load_state_dict(reference_pixel_weights())`` loads it strictly."""
-    g = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(__file__))), "tests", "golden")
     sd = {}
     for name in ("pixel_policy_cnn.npz", "pixel_policy_cnn_conv3.npz"):
-        with np.load(os.path.join(g, name), allow_pickle=False) as d:
+        with np.load(golden(name, required=True), allow_pickle=False) as d:
             for k in d.files:
                 sd[k] = torch.from_numpy(np.array(d[k]))
     for i in (1, 2, 3):             # not a weight, not in the fixture: a fresh module's value
@@ -123,7 +118,9 @@ def reference_pixel_weights() -> dict:
     return {k: sd[k] for k in PixelPolicy().state_dict()}
 
 
-class HipPixelPolicy:
+
+
+class HipPixelPolicy(HipHandle):
     """``be_cnn_act`` bound to one BatchedBallEnv.
 
     ``load(policy)`` packs the module's current fp32 weights and BatchNorm buffers on the device (one
@@ -131,42 +128,32 @@ class HipPixelPolicy:
     writes ``action`` (N,) u8, ``log_prob`` (N,) f32 and, if ``probs=True``, ``probs`` (N, A) f32.
     Owns the (N, 3, 40, 40) u8 ``image`` buffer ``act()`` observes into."""
 
-    def __init__(self, env, policy: PixelPolicy, norm: str = "sample", probs: bool = False, seed: int = 0):
+    ENTRIES = ("be_cnn_create", "be_cnn_destroy", "be_cnn_bytes")
+    SEED = 0
+
+    def __init__(self, env, policy: PixelPolicy, norm: str = "sample", probs: bool = False,
+                 seed: Optional[int] = None):
         if norm not in NORMS:
             raise ValueError("norm must be 'sample' or 'running'")
-        self.env, self.norm, self.seed = env, norm, int(seed)
-        self._lib = _abi.lib()
-        self.num_actions = int(policy.head.out_features)
-        dev, N = env.device, env.num_envs
-        self.action = torch.zeros(N, dtype=torch.uint8, device=dev)
-        self.log_prob = torch.zeros(N, dtype=torch.float32, device=dev)
-        self.probs = torch.zeros(N, self.num_actions, dtype=torch.float32, device=dev) if probs else None
-        self.image = torch.zeros(N, *IMAGE, dtype=torch.uint8, device=dev)
-        self._out = _abi.BeActOut(self.action.data_ptr(), self.log_prob.data_ptr(), None,
-                                  None if self.probs is None else self.probs.data_ptr())
-        h = C.c_void_p()
-        _abi.check(self._lib.be_cnn_create(env._ctx, self.num_actions, C.byref(h)), env._ctx)
-        self._h = h
-        self._weights = None
+        self.norm = norm
+        A = int(policy.head.out_features)
+        self.image = torch.zeros(env.num_envs, *IMAGE, dtype=torch.uint8, device=env.device)
+        super().__init__(env, (A,), A, probs, seed)
         self.load(policy)
 
     def load(self, policy: PixelPolicy) -> None:
         sd = policy.state_dict()
-        want = {k: tuple(v.shape) for k, v in PixelPolicy(self.num_actions).state_dict().items()}
+        shapes = {k: tuple(v.shape) for k, v in PixelPolicy(self.num_actions).state_dict().items()}
         if int(policy.head.out_features) != self.num_actions:
             raise ValueError("policy's num_actions does not match this HipPixelPolicy")
         for k in _abi.CNN_TENSORS:
-            if k not in sd or tuple(sd[k].shape) != want[k]:
-                raise ValueError(f"policy tensor {k} must have shape {want[k]}")
+            if k not in sd or tuple(sd[k].shape) != shapes[k]:
+                raise ValueError(f"policy tensor {k} must have shape {shapes[k]}")
         dev = self.env.device
         ws = [sd[k].detach().to(device=dev, dtype=torch.float32).contiguous() for k in _abi.CNN_TENSORS]
         w = _abi.BeCnnWeights(*[t.data_ptr() for t in ws])
         _abi.check(self._lib.be_cnn_load(self._h, C.byref(w), self.env._stream()), self.env._ctx)
         self._weights = ws          # keep alive until the packing kernel has run
-
-    @property
-    def packed_bytes(self) -> int:
-        return int(self._lib.be_cnn_bytes(self._h))
 
     def act(self, image: Optional[torch.Tensor] = None, quadrant: Optional[torch.Tensor] = None,
             seed: Optional[int] = None):
@@ -175,91 +162,36 @@ class HipPixelPolicy:
         more launch); quadrant: (N,) u8 in 0..3 (default: the goal's quadrant of the current state,
         computed in the kernel).  Nothing is allocated: capturable.  Returns (action, log_prob, probs)."""
         env, N = self.env, self.env.num_envs
-        if image is None:
-            image = env.observe_pixels(out=self.image)
-        elif image.dtype != torch.uint8 or tuple(image.shape) != (N, *IMAGE) or not image.is_contiguous() or \
-                image.device != env.device:
-            raise ValueError("image must be an (N, 3, 40, 40) contiguous u8 tensor on the env's device")
-        if quadrant is not None and (quadrant.dtype != torch.uint8 or tuple(quadrant.shape) != (N,) or
-                                     not quadrant.is_contiguous() or quadrant.device != env.device):
-            raise ValueError("quadrant must be an (N,) contiguous u8 tensor on the env's device")
-        s = self.seed if seed is None else int(seed)
+        image = env.observe_pixels(out=self.image) if image is None else \
+            want(image, "image", torch.uint8, (N, *IMAGE), env.device)
+        want(quadrant, "quadrant", torch.uint8, (N,), env.device, optional=True)
         _abi.check(self._lib.be_cnn_act(self._h, C.byref(env._st), image.data_ptr(),
                                         None if quadrant is None else quadrant.data_ptr(), NORMS[self.norm],
-                                        C.byref(self._out), s & (2**64 - 1), env._stream()), env._ctx)
+                                        C.byref(self._out), self._seed(seed), env._stream()), env._ctx)
         return self.action, self.log_prob, self.probs
 
-    def close(self) -> None:
-        if getattr(self, "_h", None) is not None:
-            torch.cuda.synchronize(self.env.device)
-            self._lib.be_cnn_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class PixelRollout:
+class PixelRollout(StepRollout):
     """T steps of every env with the pixel policy in the loop (ball_cnn_reinforce.py's episode loop,
     batched): per step ``be_observe_pixels`` writes the images (with ``record_images`` into row t of
     ``images`` (T, N, 3, 40, 40) u8), ``be_cnn_act`` writes action and log_prob into row t, then
-    ``be_step`` writes rewards and dones into row t.  The per-step out-structs point into the (T, N)
-    buffers, so there are no copy kernels; ``capture()`` records the loop into HIP graphs (a linear chain
-    on one stream) and ``run()`` replays them."""
+    ``be_step`` writes rewards and dones into row t.  The loop, its (T, N) buffers, ``capture()`` and
+    ``run()`` are ``StepRollout``'s (rollout.py)."""
 
     def __init__(self, env, policy: PixelPolicy, horizon: int, norm: str = "sample", seed: int = 0,
                  record_images: bool = False):
-        self.env, self.policy, self.T, self.seed = env, policy, int(horizon), int(seed)
-        dev, N, T = env.device, env.num_envs, self.T
-        self.actions = torch.zeros(T, N, dtype=torch.uint8, device=dev)
-        self.log_probs = torch.zeros(T, N, dtype=torch.float32, device=dev)
-        self.rewards = torch.zeros(T, N, dtype=torch.float64, device=dev)
-        self.dones = torch.zeros(T, N, dtype=torch.bool, device=dev)
-        self.images = torch.zeros(T, N, *IMAGE, dtype=torch.uint8, device=dev) if record_images else None
-        self.hp = HipPixelPolicy(env, policy, norm=norm, seed=self.seed)
-        self._lib = _abi.lib()
-        self._graphs = []
-        self._act_outs = [_abi.BeActOut(self.actions[t].data_ptr(), self.log_probs[t].data_ptr(), None, None)
-                          for t in range(T)]
-        o = env._out
-        self._step_outs = [_abi.BeOut(o.obs, o.obs_f32, self.rewards[t].data_ptr(), self.dones[t].data_ptr(),
-                                      o.truncated, o.terminal_obs, o.final_return, o.final_len, o.stats)
-                           for t in range(T)]
+        super().__init__(env, policy, HipPixelPolicy(env, policy, norm=norm, seed=int(seed)), horizon, seed)
+        self.images = torch.zeros(self.T, env.num_envs, *IMAGE, dtype=torch.uint8, device=env.device) \
+            if record_images else None
 
-    def step(self, t: int, stream_ptr=None) -> None:
-        """observe + select_action + env step of every env, results into row t."""
+    def _act(self, t: int, s) -> None:
+        """observe + select_action of every env, results into row t."""
         env, lib = self.env, self._lib
-        s = env._stream() if stream_ptr is None else stream_ptr
         img = (self.hp.image if self.images is None else self.images[t]).data_ptr()
-        calls = ((lib.be_observe_pixels, (env._ctx, C.byref(env._st), None, img, None, s)),
-                 (lib.be_cnn_act, (self.hp._h, C.byref(env._st), img, None, NORMS[self.hp.norm],
-                                   C.byref(self._act_outs[t]), self.seed & (2**64 - 1), s)),
-                 (lib.be_step, (env._ctx, C.byref(env._st), C.c_void_p(self.actions[t].data_ptr()), None, None,
-                                C.byref(self._step_outs[t]), s)))
-        for fn, args in calls:
-            rc = fn(*args)
-            if rc:
-                _abi.check(rc, env._ctx)
-
-    def run_eager(self) -> None:
-        for t in range(self.T):
-            self.step(t)
-
-    def capture(self, chunk: int = 250, stream: Optional[torch.cuda.Stream] = None) -> None:
-        """Record the T steps into HIP graphs of ``chunk`` steps each (stream: the stream to capture
-        on; default a new one from torch's pool)."""
-        self._graphs = capture_steps(self.step, self.T, chunk, self.env.device, stream)
-
-    def run(self) -> None:
-        """Replay the captured horizon (capture() first)."""
-        if not self._graphs:
-            raise RuntimeError("capture() first")
-        for g in self._graphs:
-            g.replay()
-
-    def close(self) -> None:
-        self._graphs = []
-        self.hp.close()
+        rc = lib.be_observe_pixels(env._ctx, C.byref(env._st), None, img, None, s)
+        if rc:
+            _abi.check(rc, env._ctx)
+        rc = lib.be_cnn_act(self.hp._h, C.byref(env._st), img, None, NORMS[self.hp.norm],
+                            C.byref(self._act_outs[t]), self.seed & (2**64 - 1), s)
+        if rc:
+            _abi.check(rc, env._ctx)

@@ -13,12 +13,12 @@ one launch of the hand-written kernel in csrc/policy.hip (libballenv.so,
 round trip per step, so a whole rollout captures into one HIP graph
 (see ``rollout.py``).  ``torch_select_action`` is the same computation in
 plain PyTorch fp32 -- the numerics reference of the tests and the
-``backend="torch"`` rollout.
+``backend="torch"`` rollout.  The handle's life, its output buffers and seed
+are ``_bind.HipHandle``'s, the draw ``_bind.categorical_pick``.
 """
 from __future__ import annotations
 
 import ctypes as C
-import os
 from typing import Optional
 
 import numpy as np
@@ -27,6 +27,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _abi
+from ._bind import HipHandle, categorical_pick, golden, want
 
 HIDDEN = {5: 128, 10: 208}   # ball_cnn_ac3.py:115-119
 
@@ -60,9 +61,7 @@ class Policy(nn.Module):
 
 def reference_weights(window: int) -> Optional[str]:
     """Path of the committed fixture of the reference's trained Policy(W), if any."""
-    p = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(__file__))), "tests", "golden",
-                     f"policy_w{window}.npz")
-    return p if os.path.exists(p) else None
+    return golden(f"policy_w{window}.npz")
 
 
 def torch_select_action(policy: Policy, obs: torch.Tensor, u: torch.Tensor):
@@ -70,15 +69,11 @@ def torch_select_action(policy: Policy, obs: torch.Tensor, u: torch.Tensor):
     ``a = #{j : cdf_j <= u}`` from given uniforms ``u`` (N,) -- the rule the HIP
     kernel uses.  Returns (action int64, log_prob, value, probs)."""
     probs, value = policy(obs.float())
-    cdf = probs.cumsum(-1)
-    a = (cdf <= u.unsqueeze(-1)).sum(-1)
-    nz = torch.arange(probs.shape[-1], device=probs.device).expand_as(probs).masked_fill(probs <= 0, 0)
-    a = torch.minimum(a, nz.max(-1).values)
-    logp = torch.log(probs.gather(-1, a.unsqueeze(-1))).squeeze(-1)
+    a, logp = categorical_pick(probs, u)
     return a, logp, value.squeeze(-1), probs
 
 
-class HipPolicy:
+class HipPolicy(HipHandle):
     """``be_policy_act`` bound to one BatchedBallEnv (same device, N, W).
 
     ``load(policy)`` packs the module's current fp32 weights on the device (one
@@ -87,28 +82,19 @@ class HipPolicy:
     ``value`` (N,) f32 and, if ``probs=True``, ``probs`` (N, A) f32.
     """
 
+    ENTRIES = ("be_policy_create", "be_policy_destroy", "be_policy_bytes")
+    VALUE = True
+
     def __init__(self, env, policy: Optional[Policy] = None, hidden: Optional[int] = None, num_actions: int = 9,
-                 probs: bool = False, seed: int = 0x5E1EC7):
-        self.env = env
-        self._lib = _abi.lib()
+                 probs: bool = False, seed: Optional[int] = None):
         if policy is not None:
             hidden, num_actions = policy.hidden_layer, policy.action_head.out_features
         elif hidden is None:
             hidden = HIDDEN.get(env.window)
         if hidden is None:
             raise ValueError("pass hidden= for this window size")
-        self.hidden, self.num_actions, self.seed = int(hidden), int(num_actions), int(seed)
-        dev, N = env.device, env.num_envs
-        self.action = torch.zeros(N, dtype=torch.uint8, device=dev)
-        self.log_prob = torch.zeros(N, dtype=torch.float32, device=dev)
-        self.value = torch.zeros(N, dtype=torch.float32, device=dev)
-        self.probs = torch.zeros(N, self.num_actions, dtype=torch.float32, device=dev) if probs else None
-        self._out = _abi.BeActOut(self.action.data_ptr(), self.log_prob.data_ptr(), self.value.data_ptr(),
-                                  None if self.probs is None else self.probs.data_ptr())
-        h = C.c_void_p()
-        _abi.check(self._lib.be_policy_create(env._ctx, self.hidden, self.num_actions, C.byref(h)), env._ctx)
-        self._h = h
-        self._weights = None
+        self.hidden = int(hidden)
+        super().__init__(env, (self.hidden, int(num_actions)), num_actions, probs, seed)
         if policy is not None:
             self.load(policy)
 
@@ -122,29 +108,10 @@ class HipPolicy:
         _abi.check(self._lib.be_policy_load(self._h, *[w.data_ptr() for w in ws], self.env._stream()), self.env._ctx)
         self._weights = ws          # keep alive until the packing kernel has run
 
-    @property
-    def packed_bytes(self) -> int:
-        return int(self._lib.be_policy_bytes(self._h))
-
     def act(self, obs: Optional[torch.Tensor] = None, seed: Optional[int] = None):
         """select_action for every env from ``obs`` (default: the env's u8 obs buffer)."""
-        obs = self.env.obs if obs is None else obs
-        if obs.dtype != torch.uint8 or tuple(obs.shape) != (self.env.num_envs, self.env.obs_dim) or \
-                not obs.is_contiguous() or obs.device != self.env.device:
-            raise ValueError("obs must be the (N, 4+W*W) contiguous u8 window obs on the env's device")
-        s = self.seed if seed is None else int(seed)
-        _abi.check(self._lib.be_policy_act(self._h, C.byref(self.env._st), obs.data_ptr(), C.byref(self._out),
-                                           s & (2**64 - 1), self.env._stream()), self.env._ctx)
+        env = self.env
+        obs = want(env.obs if obs is None else obs, "obs", torch.uint8, (env.num_envs, env.obs_dim), env.device)
+        _abi.check(self._lib.be_policy_act(self._h, C.byref(env._st), obs.data_ptr(), C.byref(self._out),
+                                           self._seed(seed), env._stream()), env._ctx)
         return self.action, self.log_prob, self.value, self.probs
-
-    def close(self) -> None:
-        if getattr(self, "_h", None) is not None:
-            torch.cuda.synchronize(self.env.device)
-            self._lib.be_policy_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -12,23 +12,30 @@ N envs is two launches that never leave the GPU:
 and each launch writes straight into row t of the (T, N) trajectory buffers
 (per-step ``be_out`` / ``be_act_out`` structs point into them: no copy
 kernels).  ``capture()`` records the T-step loop into HIP graphs, so
-``run()`` is one graph replay per chunk with no host work per step.
+``run()`` is one graph replay per chunk with no host work per step.  That loop
+is ``StepRollout``, the base of ``Rollout`` here, ``BlockRollout``
+(block_policy.py) and ``PixelRollout`` (pixel_policy.py): a subclass supplies
+the policy launches of one step and, where it has one, the fused launch.
 
 ``backend="fused"`` runs the same T steps as ``be_policy_rollout`` launches of ``chunk``
 steps each: select_action and the env step in one kernel, each env's state in
-registers and the packed policy in LDS (bit-identical to ``"hip"``).
+registers and the packed policy in LDS (bit-identical to ``"hip"``); ``step(t)``
+raises there, as it does for every fused rollout.
 
 ``backend="torch"`` runs select_action as plain PyTorch fp32 (``Policy`` +
 ``torch_select_action`` on ``torch.rand`` uniforms) -- the PyTorch-ROCm policy
 the BASELINE config names, kept as the comparison point.
 
 ``discounted_returns`` is the batched form of finish_episode's return
-recursion (:224-227) with episode boundaries (done) cutting the sum;
+recursion (:224-227) with episode boundaries (done) cutting the sum
+(``discounted``; with ``episode_ids`` the shared part of the two plain-torch
+target functions, ``_torch_targets`` here and block_policy's ``_episode_targets``);
 ``a2c_losses`` / ``a2c_update`` are the whole finish_episode (per-episode
 return normalisation, policy + value losses) over all envs at once, so a
 training loop is rollout (HIP) -> update (torch autograd) -> re-pack (HIP).
 ``A2CGrad`` (``a2c_update(grads="hip")``) is the losses and ``loss.backward()``
-of that update in one HIP entry (``be_a2c_grad``), straight from the u8 record.
+of that update in one HIP entry (``be_a2c_grad``), straight from the u8 record
+(optim.py's ``RowGrad`` is what it shares with ``BlockGrad``).
 ``HipAdam`` is ``optimizer.step()`` and the re-pack in one HIP entry (``be_a2c_adam``; optim.py's
 ``HipOptim`` is what it shares with the block policy's ``HipBlockOptim``), and
 ``A2CTrainer`` the loop rollout -> targets -> gradients -> Adam -> re-packed policy with no host
@@ -42,7 +49,8 @@ from typing import NamedTuple, Optional
 import torch
 
 from . import _abi
-from .optim import HipOptim, _beta_powers, is_f32      # noqa: F401  (_beta_powers stays importable from here)
+from ._bind import want
+from .optim import HipOptim, RowGrad, _beta_powers      # noqa: F401  (_beta_powers stays importable from here)
 from .policy import HipPolicy, Policy, torch_select_action
 
 
@@ -67,19 +75,12 @@ def a2c_targets(env, rewards: torch.Tensor, dones: torch.Tensor, values: Optiona
     import numpy as np
     eps = float(np.finfo(np.float32).eps) if eps is None else float(eps)
     dev, N = env.device, env.num_envs
-    if rewards.dim() != 2 or rewards.shape[1] != N or rewards.shape[0] < 1 or rewards.dtype != torch.float64 or \
-            not rewards.is_contiguous() or rewards.device != dev:
-        raise ValueError("rewards must be a (T, N) contiguous f64 tensor on the env's device")
-    T = rewards.shape[0]
-    if dones.dtype not in (torch.bool, torch.uint8) or tuple(dones.shape) != (T, N) or not dones.is_contiguous() or \
-            dones.device != dev:
-        raise ValueError("dones must be a (T, N) contiguous bool / u8 tensor on the env's device")
-    if values is not None and (values.dtype != torch.float32 or tuple(values.shape) != (T, N) or
-                               not values.is_contiguous() or values.device != dev):
-        raise ValueError("values must be a (T, N) contiguous f32 tensor on the env's device")
-    if bootstrap is not None and (bootstrap.dtype != torch.float64 or tuple(bootstrap.shape) != (N,) or
-                                  not bootstrap.is_contiguous() or bootstrap.device != dev):
-        raise ValueError("bootstrap must be an (N) contiguous f64 tensor on the env's device")
+    T = want(rewards, "rewards", torch.float64, (None, N), dev).shape[0]
+    if T < 1:
+        raise ValueError("rewards must have at least one row")
+    want(dones, "dones", (torch.bool, torch.uint8), (T, N), dev)
+    want(values, "values", torch.float32, (T, N), dev, optional=True)
+    want(bootstrap, "bootstrap", torch.float64, (N,), dev, optional=True)
     rn = torch.empty(T, N, dtype=torch.float32, device=dev)
     adv = torch.empty(T, N, dtype=torch.float32, device=dev) if values is not None else None
     valid = torch.empty(T, N, dtype=torch.uint8, device=dev)
@@ -103,72 +104,34 @@ _PARAMS = ("fc1.weight", "fc1.bias", "action_head.weight", "action_head.bias", "
            "value_head.bias")
 
 
-class A2CGrad:
+class A2CGrad(RowGrad):
     """``be_a2c_grad`` bound to one BatchedBallEnv and one Policy: the policy and value loss sums of
     ``a2c_losses`` and what ``loss.backward()`` leaves in the six ``.grad``, from the recorded u8
-    observations in two launches (include/ballenv.h pins the arithmetic; reproducible bit for bit).
+    observations in two launches.  The workspace, the six gradient tensors (``.grads``), the f64 ``_losses``,
+    the checks and ``assign()``: ``RowGrad`` (optim.py)."""
 
-    Owns the workspace, the six gradient tensors (``.grads``, keyed like ``policy.state_dict()``)
-    and the f64 ``losses``; nothing is allocated per call, so a call can be graph-captured.  The
-    weights are read from the module's parameters at call time (fp32, contiguous, on the env's
-    device)."""
+    LOSS_WIDTH = 3
+    WEIGHTS, GRADS = _abi.BeA2CWeights, _abi.BeA2CGrads
 
     def __init__(self, env, policy: Policy):
-        self.env, self.policy = env, policy
-        self._lib = _abi.lib()
-        dev = env.device
         self.hidden, self.num_actions = int(policy.hidden_layer), int(policy.action_head.out_features)
         if policy.fc1.in_features != env.obs_dim:
             raise ValueError("policy input size does not match the env's observation")
-        nbytes = int(self._lib.be_a2c_grad_workspace_bytes(env._ctx, self.hidden, self.num_actions))
-        if nbytes < 0:
-            _abi.check(nbytes, env._ctx)
-        self.workspace = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
-        sd = policy.state_dict()
-        self.grads = {k: torch.zeros(sd[k].shape, dtype=torch.float32, device=dev) for k in _PARAMS}
-        self._losses = torch.zeros(3, dtype=torch.float64, device=dev)
-        self._g = _abi.BeA2CGrads(*(self.grads[k].data_ptr() for k in _PARAMS), self._losses.data_ptr())
-        self._weights = None
-
-    def _params(self):
-        ps = dict(self.policy.named_parameters())
-        ws = [ps[k].detach() for k in _PARAMS]
-        for k, w in zip(_PARAMS, ws):
-            if not is_f32(w, self.grads[k].shape, self.env.device):
-                raise ValueError(f"policy parameter {k} must be a contiguous f32 tensor of the shape A2CGrad was "
-                                 "made for, on the env's device")
-        return ws
+        sizes = (self.hidden, self.num_actions)
+        super().__init__(env, policy, _PARAMS, "be_a2c_grad_workspace_bytes", sizes, sizes)
 
     def __call__(self, obs: torch.Tensor, actions: torch.Tensor, returns_norm: torch.Tensor, valid: torch.Tensor):
         """obs (T, N, F) or (rows, F) u8; actions u8, returns_norm f32, valid u8 or bool, each (T, N) or
         (rows,): contiguous, on the env's device.  Asynchronous on the caller's current stream.
         Returns ``.grads``."""
-        dev, F = self.env.device, self.env.obs_dim
-        if obs.dtype != torch.uint8 or obs.dim() not in (2, 3) or obs.shape[-1] != F or not obs.is_contiguous() or \
-                obs.device != dev:
-            raise ValueError("obs must be a (T, N, F) or (rows, F) contiguous u8 tensor on the env's device")
-        lead = tuple(obs.shape[:-1])
-        if actions.dtype != torch.uint8 or tuple(actions.shape) != lead or not actions.is_contiguous() or \
-                actions.device != dev:
-            raise ValueError("actions must be a contiguous u8 tensor of obs' leading shape on the env's device")
-        if returns_norm.dtype != torch.float32 or tuple(returns_norm.shape) != lead or \
-                not returns_norm.is_contiguous() or returns_norm.device != dev:
-            raise ValueError("returns_norm must be a contiguous f32 tensor of obs' leading shape on the env's device")
-        if valid.dtype not in (torch.bool, torch.uint8) or tuple(valid.shape) != lead or not valid.is_contiguous() or \
-                valid.device != dev:
-            raise ValueError("valid must be a contiguous bool / u8 tensor of obs' leading shape on the env's device")
-        rows = 1
-        for n in lead:
-            rows *= int(n)
-        ws = self._params()
-        w = _abi.BeA2CWeights(*(x.data_ptr() for x in ws), self.hidden, self.num_actions)
+        rows = self._rows(obs, "obs", self.env.obs_dim,
+                          ((actions, "actions", torch.uint8, False), (returns_norm, "returns_norm", torch.float32, False),
+                           (valid, "valid", (torch.bool, torch.uint8), False)))
+        ws, w = self._params()
         rc = self._lib.be_a2c_grad(self.env._ctx, obs.data_ptr(), actions.data_ptr(), returns_norm.data_ptr(),
                                    valid.data_ptr(), rows, C.byref(w), self.workspace.data_ptr(),
                                    self.workspace.numel() * 8, C.byref(self._g), self.env._stream())
-        if rc:
-            _abi.check(rc, self.env._ctx)
-        self._weights = ws          # keep alive until the kernels have run
-        return self.grads
+        return self._ran(rc, ws)
 
     def losses(self):
         """(policy_loss, value_loss, count) of the last call as Python numbers (synchronises)."""
@@ -215,7 +178,7 @@ def capture_graph(fn, dev, stream: Optional[torch.cuda.Stream] = None) -> torch.
 
 def capture_steps(step, T: int, chunk: int, dev, stream: Optional[torch.cuda.Stream] = None) -> list:
     """``step(t, stream_ptr)`` for t = 0 .. T - 1 recorded into HIP graphs of ``chunk`` steps each, all on
-    one stream: what ``Rollout.capture`` and ``BlockRollout.capture`` keep in ``_graphs``."""
+    one stream: what ``StepRollout.capture`` keeps in ``_graphs``."""
     cap = torch.cuda.Stream(dev) if stream is None else stream
     chunk = max(1, int(chunk))
 
@@ -226,89 +189,77 @@ def capture_steps(step, T: int, chunk: int, dev, stream: Optional[torch.cuda.Str
     return [capture_graph(lambda: steps(c0), dev, cap) for c0 in range(0, T, chunk)]
 
 
-class Rollout:
-    def __init__(self, env, policy: Policy, horizon: int, backend: str = "hip", record_obs: bool = False,
-                 seed: int = 0x5E1EC7, chunk: int = 100):
-        if backend not in ("hip", "fused", "torch"):
-            raise ValueError("backend must be 'hip', 'fused' or 'torch'")
-        self.env, self.policy, self.T, self.backend = env, policy, int(horizon), backend
+class StepRollout:
+    """The T-step loop of the three policies: per step the subclass's policy launches (``_act``), then
+    ``be_step``, each writing straight into row t of the (T, N) ``actions`` u8 / ``log_probs`` f32 /
+    ``values`` f32 (None without a value head) / ``rewards`` f64 / ``dones`` bool through the per-step
+    ``_act_outs`` / ``_step_outs`` structs (no copy kernels).  ``capture()`` records the loop into HIP
+    graphs (a linear chain on one stream) and ``run()`` replays them.
+
+    ``backend="fused"``, where the subclass has one: the same T steps as launches of ``chunk`` steps each
+    (``_launch``); nothing to capture then, ``run()`` and ``run_eager()`` both issue them, ``step(t)`` raises.
+
+    obs_rows: a tensor whose row t receives the window obs step t writes (default: the env's obs buffer).
+    ``begin()`` / ``end()`` bracket a horizon (nothing here)."""
+
+    def __init__(self, env, policy, hp, horizon: int, seed: int, backend: str = "hip", chunk: int = 100,
+                 values: bool = False, obs_rows: Optional[torch.Tensor] = None):
+        self.env, self.policy, self.hp, self.T, self.seed = env, policy, hp, int(horizon), int(seed)
+        self.backend, self.chunk = backend, max(1, int(chunk))
         dev, N, T = env.device, env.num_envs, self.T
-        self.seed = int(seed)
         self.actions = torch.zeros(T, N, dtype=torch.uint8, device=dev)
         self.log_probs = torch.zeros(T, N, dtype=torch.float32, device=dev)
-        self.values = torch.zeros(T, N, dtype=torch.float32, device=dev)
+        self.values = torch.zeros(T, N, dtype=torch.float32, device=dev) if values else None
         self.rewards = torch.zeros(T, N, dtype=torch.float64, device=dev)
         self.dones = torch.zeros(T, N, dtype=torch.bool, device=dev)
-        self.obs = torch.zeros(T + 1, N, env.obs_dim, dtype=torch.uint8, device=dev) if record_obs else None
         self._graphs = []
         self._lib = _abi.lib()
-        self.chunk = max(1, int(chunk))
-        if backend in ("hip", "fused"):
-            self.hp = HipPolicy(env, policy, seed=self.seed)
-            self._act_outs = [_abi.BeActOut(self.actions[t].data_ptr(), self.log_probs[t].data_ptr(),
-                                            self.values[t].data_ptr(), None) for t in range(T)]
-        else:
-            self.hp = None
-            self.policy = policy.to(dev)     # draws: torch.rand on the default (graph-safe) generator
+        self._act_outs = [self._act_out(t) for t in range(T)]
         o = env._out
-        self._step_outs = []
-        for t in range(T):
-            obs_ptr = self.obs[t + 1].data_ptr() if record_obs else o.obs
-            self._step_outs.append(_abi.BeOut(obs_ptr, o.obs_f32, self.rewards[t].data_ptr(),
-                                              self.dones[t].data_ptr(), o.truncated, o.terminal_obs,
-                                              o.final_return, o.final_len, o.stats))
+        self._step_outs = [_abi.BeOut(o.obs if obs_rows is None else obs_rows[t].data_ptr(), o.obs_f32,
+                                      self.rewards[t].data_ptr(), self.dones[t].data_ptr(), o.truncated,
+                                      o.terminal_obs, o.final_return, o.final_len, o.stats) for t in range(T)]
+
+    def _act_out(self, t: int):
+        """The be_act_out whose outputs start at row t."""
+        return _abi.BeActOut(self.actions[t].data_ptr(), self.log_probs[t].data_ptr(),
+                             None if self.values is None else self.values[t].data_ptr(), None)
+
+    def _chunk_out(self, c0: int, obs_ptr):
+        """The be_out of a fused launch whose rewards and dones start at row c0."""
+        return _abi.BeOut(obs_ptr, None, self.rewards[c0].data_ptr(), self.dones[c0].data_ptr(), None, None,
+                          None, None, self.env._out.stats)
 
     def run_fused(self, stream_ptr=None) -> None:
-        """The horizon as be_policy_rollout launches of ``chunk`` steps (backend="fused")."""
-        env, lib, N, F = self.env, self._lib, self.env.num_envs, self.env.obs_dim
+        """The horizon as fused launches of ``chunk`` steps (backend="fused")."""
+        env = self.env
         s = env._stream() if stream_ptr is None else stream_ptr
         self.begin()
         for c0 in range(0, self.T, self.chunk):
-            k = min(self.chunk, self.T - c0)
-            rec = self.obs[c0 + 1].data_ptr() if self.obs is not None else None
-            out = _abi.BeOut(rec, None, self.rewards[c0].data_ptr(), self.dones[c0].data_ptr(), None, None,
-                             None, None, env._out.stats)
-            act = _abi.BeActOut(self.actions[c0].data_ptr(), self.log_probs[c0].data_ptr(),
-                                self.values[c0].data_ptr(), None)
-            rc = lib.be_policy_rollout(self.hp._h, C.byref(env._st), env.obs.data_ptr(), env.obs.data_ptr(), k,
-                                       C.byref(out), C.byref(act), self.seed & (2**64 - 1), s)
+            rc = self._launch(c0, min(self.chunk, self.T - c0), self._act_out(c0), s)
             if rc:
                 _abi.check(rc, env._ctx)
-
-    def _obs_t(self, t: int) -> torch.Tensor:
-        return self.obs[t] if self.obs is not None else self.env.obs
 
     def step(self, t: int, stream_ptr=None) -> None:
-        """select_action + env step of every env, results into row t."""
-        env, lib = self.env, self._lib
+        """The policy's select_action + env step of every env, results into row t."""
+        if self.backend == "fused":
+            raise RuntimeError("backend='fused' has no single step: run() / run_eager() issue the fused launches")
+        env = self.env
         s = env._stream() if stream_ptr is None else stream_ptr
-        obs = self._obs_t(t)
-        if self.backend == "hip":
-            rc = lib.be_policy_act(self.hp._h, C.byref(env._st), obs.data_ptr(), C.byref(self._act_outs[t]),
-                                   self.seed & (2**64 - 1), s)
-            if rc:
-                _abi.check(rc, env._ctx)
-        else:
-            with torch.no_grad():
-                u = torch.rand(env.num_envs, device=env.device)
-                a, lp, v, _ = torch_select_action(self.policy, obs, u)
-                self.actions[t].copy_(a)
-                self.log_probs[t].copy_(lp)
-                self.values[t].copy_(v)
-        rc = lib.be_step(env._ctx, C.byref(env._st), C.c_void_p(self.actions[t].data_ptr()), None, None,
-                         C.byref(self._step_outs[t]), s)
+        self._act(t, s)
+        rc = self._lib.be_step(env._ctx, C.byref(env._st), C.c_void_p(self.actions[t].data_ptr()), None, None,
+                               C.byref(self._step_outs[t]), s)
         if rc:
             _abi.check(rc, env._ctx)
 
     def begin(self) -> None:
-        """Make row 0 of the obs record the env's current obs (call after reset)."""
-        if self.obs is not None:
-            self.obs[0].copy_(self.env.obs)
+        pass
 
     def end(self) -> None:
-        """With record_obs the steps write obs into the record: leave the last one in env.obs."""
-        if self.obs is not None:
-            self.env.obs.copy_(self.obs[self.T])
+        pass
+
+    def _warm(self) -> None:
+        """What must run eagerly once before a capture (nothing here)."""
 
     def run_eager(self) -> None:
         if self.backend == "fused":
@@ -321,16 +272,11 @@ class Rollout:
     def capture(self, chunk: int = 250, stream: Optional[torch.cuda.Stream] = None) -> None:
         """Record the T steps into HIP graphs of ``chunk`` steps each (stream: the stream to capture
         on; default a new one from torch's pool)."""
-        dev = self.env.device
         if self.backend == "fused":     # a few launches per horizon: nothing to capture
             self._graphs = []
             return
-        if self.backend == "torch":
-            # initialise the BLAS handles eagerly: hipBLASLt set-up is not capturable
-            with torch.no_grad():
-                self.policy(self.env.obs[:64].float())
-            torch.cuda.synchronize(dev)
-        self._graphs = capture_steps(self.step, self.T, chunk, dev, stream)
+        self._warm()
+        self._graphs = capture_steps(self.step, self.T, chunk, self.env.device, stream)
 
     def run(self) -> None:
         """Replay the captured horizon (capture() first)."""
@@ -343,45 +289,113 @@ class Rollout:
             g.replay()
         self.end()
 
-    def discounted_returns(self, gamma: float = 0.99, bootstrap: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """R_t = r_t + gamma * R_{t+1} * (1 - done_t), per env (finish_episode, ball_cnn_ac3.py:224-227)."""
-        R = torch.zeros(self.env.num_envs, dtype=torch.float64, device=self.env.device) if bootstrap is None \
-            else bootstrap.to(torch.float64).clone()
-        out = torch.empty_like(self.rewards)
-        for t in range(self.T - 1, -1, -1):
-            R = self.rewards[t] + gamma * R * (~self.dones[t]).to(torch.float64)
-            out[t] = R
-        return out
-
-    def targets(self, gamma: float = 0.99, bootstrap: Optional[torch.Tensor] = None,
-                with_returns: bool = True) -> A2CTargets:
-        """``a2c_targets`` of this rollout's rewards, dones and values (one HIP kernel)."""
-        return a2c_targets(self.env, self.rewards, self.dones, self.values, gamma, None, bootstrap, with_returns)
-
     def close(self) -> None:
         self._graphs = []
         if self.hp is not None:
             self.hp.close()
 
 
+class Rollout(StepRollout):
+    """``StepRollout`` with the A2C ``Policy``: ``be_policy_act`` + ``be_step`` per step ("hip"),
+    ``be_policy_rollout`` launches ("fused") or select_action in plain PyTorch ("torch": ``hp`` is None).
+    record_obs: ``obs`` (T + 1, N, F) u8, row t the obs action t was chosen from."""
+
+    def __init__(self, env, policy: Policy, horizon: int, backend: str = "hip", record_obs: bool = False,
+                 seed: int = 0x5E1EC7, chunk: int = 100):
+        if backend not in ("hip", "fused", "torch"):
+            raise ValueError("backend must be 'hip', 'fused' or 'torch'")
+        dev = env.device
+        self.obs = torch.zeros(int(horizon) + 1, env.num_envs, env.obs_dim, dtype=torch.uint8, device=dev) \
+            if record_obs else None
+        hp = HipPolicy(env, policy, seed=int(seed)) if backend != "torch" else None
+        super().__init__(env, policy, hp, horizon, seed, backend, chunk, values=True,
+                         obs_rows=None if self.obs is None else self.obs[1:])
+        if hp is None:
+            self.policy = policy.to(dev)     # draws: torch.rand on the default (graph-safe) generator
+
+    def _launch(self, c0: int, k: int, act, s) -> int:
+        env = self.env
+        out = self._chunk_out(c0, self.obs[c0 + 1].data_ptr() if self.obs is not None else None)
+        return self._lib.be_policy_rollout(self.hp._h, C.byref(env._st), env.obs.data_ptr(), env.obs.data_ptr(), k,
+                                           C.byref(out), C.byref(act), self.seed & (2**64 - 1), s)
+
+    def _act(self, t: int, s) -> None:
+        env = self.env
+        obs = self.obs[t] if self.obs is not None else env.obs
+        if self.hp is not None:
+            rc = self._lib.be_policy_act(self.hp._h, C.byref(env._st), obs.data_ptr(), C.byref(self._act_outs[t]),
+                                         self.seed & (2**64 - 1), s)
+            if rc:
+                _abi.check(rc, env._ctx)
+        else:
+            with torch.no_grad():
+                u = torch.rand(env.num_envs, device=env.device)
+                a, lp, v, _ = torch_select_action(self.policy, obs, u)
+                self.actions[t].copy_(a)
+                self.log_probs[t].copy_(lp)
+                self.values[t].copy_(v)
+
+    def begin(self) -> None:
+        """Make row 0 of the obs record the env's current obs (call after reset)."""
+        if self.obs is not None:
+            self.obs[0].copy_(self.env.obs)
+
+    def end(self) -> None:
+        """With record_obs the steps write obs into the record: leave the last one in env.obs."""
+        if self.obs is not None:
+            self.env.obs.copy_(self.obs[self.T])
+
+    def _warm(self) -> None:
+        if self.hp is None:
+            # initialise the BLAS handles eagerly: hipBLASLt set-up is not capturable
+            with torch.no_grad():
+                self.policy(self.env.obs[:64].float())
+            torch.cuda.synchronize(self.env.device)
+
+    def discounted_returns(self, gamma: float = 0.99, bootstrap: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """R_t = r_t + gamma * R_{t+1} * (1 - done_t), per env (finish_episode, ball_cnn_ac3.py:224-227)."""
+        return discounted(self.rewards, self.dones, gamma, bootstrap)
+
+    def targets(self, gamma: float = 0.99, bootstrap: Optional[torch.Tensor] = None,
+                with_returns: bool = True) -> A2CTargets:
+        """``a2c_targets`` of this rollout's rewards, dones and values (one HIP kernel)."""
+        return a2c_targets(self.env, self.rewards, self.dones, self.values, gamma, None, bootstrap, with_returns)
+
+
+def discounted(rewards: torch.Tensor, dones: torch.Tensor, gamma: float,
+               bootstrap: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The return recursion R_t = r_t + gamma R_{t+1} (1 - done_t) per env in f64, (T, N); R_T = bootstrap (N)
+    or 0.  The one loop of ``_torch_targets``, block_policy's ``_episode_targets`` and
+    ``Rollout.discounted_returns``."""
+    T, N = rewards.shape
+    keep = 1.0 - dones.to(torch.float64)
+    acc = torch.zeros(N, dtype=torch.float64, device=rewards.device) if bootstrap is None \
+        else bootstrap.to(torch.float64).clone()
+    R = torch.empty(T, N, dtype=torch.float64, device=rewards.device)
+    for t in range(T - 1, -1, -1):
+        acc = rewards[t].to(torch.float64) + gamma * acc * keep[t]
+        R[t] = acc
+    return R
+
+
+def episode_ids(dones: torch.Tensor):
+    """(sid, S): the episode id 0 .. S - 1 of every (t, env), flat (T*N) -- dones strictly before t in that
+    env, then env -- and the number of episodes."""
+    N = dones.shape[1]
+    d = dones.to(torch.int64)
+    seg = (torch.cumsum(d, 0) - d) * N + torch.arange(N, device=dones.device)
+    _, sid = torch.unique(seg.reshape(-1), return_inverse=True)
+    return sid, int(sid.max()) + 1
+
+
 def _torch_targets(rewards: torch.Tensor, dones: torch.Tensor, gamma: float = 0.99, eps: Optional[float] = None):
-    """The per-episode normalised returns of ``a2c_losses`` in plain torch: (Rn, valid), flat (T*N)."""
+    """The per-episode normalised returns of ``a2c_losses`` in plain torch: (Rn, valid), flat (T*N).
+    The episode statistics are taken in f32."""
     import numpy as np
     eps = float(np.finfo(np.float32).eps) if eps is None else eps
-    T, N = rewards.shape
     dev = rewards.device
-    d64 = dones.to(torch.float64)
-    R = torch.empty(T, N, dtype=torch.float64, device=dev)
-    acc = torch.zeros(N, dtype=torch.float64, device=dev)
-    for t in range(T - 1, -1, -1):
-        acc = rewards[t].to(torch.float64) + gamma * acc * (1.0 - d64[t])
-        R[t] = acc
-    R32 = R.to(torch.float32)
-    # episode id of every (t, env): dones strictly before t in that env, then env
-    seg = (torch.cumsum(dones.to(torch.int64), 0) - dones.to(torch.int64)) * N + torch.arange(N, device=dev)
-    _, sid = torch.unique(seg.reshape(-1), return_inverse=True)
-    S = int(sid.max()) + 1
-    flat = R32.reshape(-1)
+    flat = discounted(rewards, dones, gamma).to(torch.float32).reshape(-1)
+    sid, S = episode_ids(dones)
     cnt = torch.bincount(sid, minlength=S).to(torch.float32)
     mean = torch.zeros(S, device=dev).index_add_(0, sid, flat) / cnt
     dev2 = (flat - mean[sid]) ** 2
@@ -445,11 +459,7 @@ def _a2c_update_hip_grads(rollout: "Rollout", optimizer, gamma: float, targets: 
         optimizer.step(grads, ag._losses)
         pl, vl, _ = ag.losses()
         return pl + vl
-    for k, prm in rollout.policy.named_parameters():
-        if prm.grad is None:
-            prm.grad = grads[k].clone()
-        else:
-            prm.grad.copy_(grads[k])
+    ag.assign()
     pl, vl, _ = ag.losses()
     optimizer.step()
     if rollout.hp is not None:
