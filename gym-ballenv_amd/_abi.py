@@ -23,7 +23,7 @@ LIB_PATH = os.environ.get("BALLENV_LIB") or os.path.join(os.path.dirname(os.path
 
 # Names declared in include/ballenv.h (checked by tests/test_abi.py).
 EXPORTS = ("be_abi_version", "be_config_default", "be_config_check", "be_step_bytes", "be_stats_slots",
-           "be_last_error", "be_kernel_name",
+           "be_last_error", "be_kernel_name", "be_step_instance",
            "be_create", "be_destroy", "be_reset", "be_step", "be_step_n", "be_rollout", "be_observe", "be_sample_actions",
            "be_status", "be_state_blob_bytes", "be_save_state", "be_load_state",
            "be_pool_fill", "be_pool_invalidate", "be_pool_set_period", "be_pool_period", "be_pool_bytes", "be_pool_entry", "be_policy_create", "be_policy_destroy", "be_policy_load", "be_policy_act",
@@ -183,6 +183,7 @@ def lib() -> C.CDLL:
         "be_stats_slots": (i64, [P(BeConfig)]),
         "be_last_error": (C.c_char_p, [vp]),
         "be_kernel_name": (C.c_char_p, [vp, i32]),
+        "be_step_instance": (i32, [vp]),
         "be_create": (C.c_int, [P(BeConfig), i32, P(vp)]),
         "be_destroy": (C.c_int, [vp]),
         "be_reset": (C.c_int, [vp, P(BeState), vp, vp, i32, P(BeOut), vp]),
@@ -249,7 +250,8 @@ def lib() -> C.CDLL:
     for name, (res, args) in sig.items():
         fn = getattr(L, name, None)
         if fn is None and diag and (name.startswith("be_pool_") or name.startswith("be_mlp_") or name.startswith("be_cnn_") or
-                                     name in ("be_board_pool_bytes", "be_a2c_adam", "be_observe_pixels", "be_pixels_coeffs")):
+                                     name in ("be_board_pool_bytes", "be_a2c_adam", "be_observe_pixels", "be_pixels_coeffs",
+                                              "be_step_instance")):
             continue
         if fn is None:
             raise BallEnvError(f"{LIB_PATH} does not export {name}: rebuild it")

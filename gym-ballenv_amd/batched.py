@@ -349,6 +349,12 @@ class BatchedBallEnv:
         r = self._lib.be_kernel_name(self._ctx, ids[entry])
         return r.decode() if r else None
 
+    def step_instance(self) -> str:
+        """Which instance of its kernel the last :meth:`step` / :meth:`step_n` launched: ``"none"``,
+        ``"plain"`` or ``"wide"`` (step2_kernel's wide obstacle-row loads: a batch that is a multiple
+        of 32 with 16-byte aligned obstacle arrays; the results are the same bits either way)."""
+        return ("none", "plain", "wide")[int(self._lib.be_step_instance(self._ctx))]
+
     # ------------------------------------------------------------------ the autoreset pool
     # (include/ballenv.h: precomputed next-episode resets the fixed-shape step kernels copy on done;
     # results are bit-identical with or without it -- these calls change timing only)

@@ -33,6 +33,8 @@ struct be_ctx {
   bool unit_moves;     // every action move in {-1,0,1}^2 (fixed-shape kernels' packed table)
   bool distinct_goals; // >= 2 pairwise-distinct goals (fixed-shape kernels' arithmetic newGoalList)
   int step_lanes;      // W = 10: lanes per env of the fixed step kernel (1: be_kernel; 2: step2_kernel)
+  int step2_wide;      // BALLENV_STEP2_WIDE as read at create (-1: step2_wide()'s rule per call; 0 / 1: forced, A/B)
+  int step_instance;   // which instance the last be_step / be_step_n launch took (STEP_INSTANCE_*; be_step_instance)
   int step5_lpe;       // W = 5: lanes per env of the fixed step kernel (1: be_kernel; 4 / 8: stepw_kernel)
   int roll5_lpe;       // W = 5: lanes per env of the fused rollout (1: rollout_kernel; 4 / 8: rolloutw_kernel)
   int max_lds;         // the device's LDS bytes per workgroup
@@ -240,6 +242,8 @@ const char* be_kernel_name(const be_ctx* ctx, int32_t entry) {
   return name;
 }
 
+int32_t be_step_instance(const be_ctx* ctx) { return ctx ? ctx->step_instance : STEP_INSTANCE_NONE; }
+
 int64_t be_stats_slots(const be_config* c) {
   if (!c || c->num_envs < 1 || c->window < 1) return 0;
   // one slot per 32 envs: the fixed-shape kernels settle stats per half-wave (LPE 1) or per
@@ -320,6 +324,7 @@ int be_create(const be_config* cfg, int32_t device, be_ctx** out) {
   // (four lanes per env, step2_kernel<10, 13, 5, 4, 128> of commit b0bc389, was bit-exact but slower
   // at every size: 6.08 vs 5.28 us at 32 768 envs, profiles/r04_w10_lanes_2_4.jsonl)
   env_lanes("BALLENV_STEP_LPE", {1, 2}, ctx->step_lanes);
+  ctx->step2_wide = step2_wide_env(getenv("BALLENV_STEP2_WIDE"));   // (A/B and the tests: forces either instance)
   if (hipDeviceGetAttribute(&ctx->max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess ||
       ctx->max_lds <= 0)
     ctx->max_lds = 65536;
@@ -437,8 +442,11 @@ static int launch(be_ctx* ctx, int mode, KParams& a, void* stream, int32_t steps
   const Launch L = mode == MODE_STEP ? (use_pool ? ctx->step_launch_pool : ctx->step_launch[fixed ? 1 : 0])
                                      : pick_kernel(ctx->cfg, mode);
   const int N = ctx->cfg.num_envs;
+  // step2_kernel's wide-row-load instance, by this call's state: whole waves, 16-byte aligned obstacle arrays
+  const bool wide = L.fn2_wide && a.prev_read && step2_wide(N, a.static_obs, a.dyn_obs, a.dyn_goal, ctx->step2_wide);
+  if (mode == MODE_STEP) ctx->step_instance = wide ? STEP_INSTANCE_WIDE : STEP_INSTANCE_PLAIN;
   for (int32_t s = 0; s < steps; ++s) {
-    launch_kernel(L, a, (hipStream_t)stream);
+    launch_kernel(L, a, (hipStream_t)stream, wide);
     a.actions += N;
     if (use_pool && ctx->book.fill_due()) launch_pool_fill(ctx, a, stream);
   }

@@ -102,6 +102,11 @@ template <class T>
 __device__ __forceinline__ T ld_s(const T* base, uint32_t idx) {
   return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + (size_t)(idx * (uint32_t)sizeof(T)));
 }
+// a T at byte offset off of a uniform base: the same addressing, for loads wider than the array's element
+template <class T, class B>
+__device__ __forceinline__ T ld_sb(const B* base, uint32_t off) {
+  return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + (size_t)off);
+}
 // Output / state stores of the fixed-shape step kernels: write-through (sc1, a relaxed agent-scope
 // atomic store), so the stores drain while the wave runs instead of in the kernel-end L2 write-back.
 // Copy-out store kinds: the step kernels write through (sc1); the fused rollouts' per-step obs rows
@@ -1737,13 +1742,24 @@ struct Step2Lds {
   static constexpr int SLOTS = (NSC + 1) / 2 + (NDC + 1) / 2 + 1;
   static constexpr size_t stage = (size_t)SLOTS * S2_CT * 4;
   static constexpr int bytes = SLOTS * S2_CT * 4 + (S2_CT / 2) * Geo<WT>::F;
+  // The WIDE instance's row exchange lies in the wave's own 32 rows of the obs stage, which nothing
+  // touches before obs_out: [16 static row slots][8 dynamic row slots] of 32 envs x 4 B, then 8
+  // dyn_goal row slots of 32 B.  A load's 64 lanes fill 8 row slots, so the slots past the arrays'
+  // rows hold a copy of the last row -- what the odd lane's masked slot reads.
+  static constexpr int XROW = 32 * 4, XDYN = 16 * XROW, XGOAL = XDYN + 8 * XROW, XBYTES = XGOAL + 8 * 32;
+  static_assert(NSC > 8 && NSC <= 16 && NDC <= 8, "two static row loads and one dynamic one per wave");
+  static_assert(XBYTES <= 32 * Geo<WT>::F && (32 * Geo<WT>::F) % 16 == 0 && stage % 16 == 0,
+                "the exchange fits a wave's stage rows, 16-byte aligned");
 };
 static_assert(S2_CT != 256 || Step2Lds<10, 13, 5>::bytes == 24576, "the default shape's LDS");
+static_assert(Step2Lds<10, 13, 5>::XBYTES == 3328, "the exchange takes the wave's whole stage at the default shape");
 // where step2_kernel's KParams argument lies in its kernarg segment: six pointers and two ints, KHot
 // on the next 64-byte line, then the KParams (KFn2, step_types.h)
 constexpr int S2_KPARAMS_AT = (6 * 8 + 2 * 4 + 63) / 64 * 64 + (int)sizeof(KHot);
 static_assert(S2_KPARAMS_AT == 128 && alignof(KParams) <= 64, "step2_kernel's kernarg layout");
-template <int WT, int NSC, int NDC, bool POOL = false, bool PREVR = true>
+// WIDE (launched only with N % 32 == 0 and 16-byte aligned obstacle arrays, behost::step2_wide):
+// the wave's obstacle rows arrive 16 bytes per lane and are spread over the pairs through LDS.
+template <int WT, int NSC, int NDC, bool POOL = false, bool PREVR = true, bool WIDE = false>
 __global__ __launch_bounds__(S2_CT, 2) void step2_kernel(const Tables* a_tables, uint32_t* a_episode, int32_t* a_ep_len,
                                                          int32_t* a_dyn_obs, uint8_t* a_dyn_goal, int32_t* a_static_obs,
                                                          int32_t a_n, int32_t a_gid0, KHot hot_in, KParams p_arg) {
@@ -1793,14 +1809,33 @@ __global__ __launch_bounds__(S2_CT, 2) void step2_kernel(const Tables* a_tables,
   const int len0 = ld_s(a_ep_len, ic);
   int32_t dp[SD], so[SS];
   int dgi[SD];
+  // WIDE: row r of an (rows, N) int32 array is, for the wave's 32 envs, 128 contiguous bytes: lane l
+  // loads 16 of them -- row l >> 3, envs 4 (l & 7) .. +3 -- so four loads (two static, one dynamic,
+  // one dword of dyn_goal's 32-byte rows) bring in what took 13 with every lane fetching 4 bytes
+  // (1 byte) of its own env.  A lane whose row is past the array re-reads the last row, as the
+  // masked slot does; a wave past N (the last block's) reads the last wave's rows, and below every
+  // lane of it takes that wave's last env, the env N - 1 that ic names.  No branch, no exec mask.
+  using XL = Step2Lds<WT, NSC, NDC>;
+  [[maybe_unused]] uint4 xs0, xs1, xd;
+  [[maybe_unused]] uint32_t xg;
+  [[maybe_unused]] const uint32_t e0c = (uint32_t)min(e0, N - EPW);
+  if constexpr (WIDE) {
+    const uint32_t r = (uint32_t)lane >> 3, c = e0c + 4u * ((uint32_t)lane & 7u);
+    const uint32_t rd = min(r, (uint32_t)(NDC - 1)) * (uint32_t)N + c;
+    xd = ld_sb<uint4>(a_dyn_obs, rd * 4u);
+    xg = ld_sb<uint32_t>(a_dyn_goal, rd);
+    xs0 = ld_sb<uint4>(a_static_obs, (r * (uint32_t)N + c) * 4u);
+    xs1 = ld_sb<uint4>(a_static_obs, (min(8u + r, (uint32_t)(NSC - 1)) * (uint32_t)N + c) * 4u);
+  } else {
 #pragma unroll
-  for (int j = 0; j < SD; ++j) {
-    const uint32_t e = (uint32_t)min(L * j + h, NDC - 1) * (uint32_t)N + ic;
-    dp[j] = ld_s(a_dyn_obs, e);
-    dgi[j] = ld_s(a_dyn_goal, e);
+    for (int j = 0; j < SD; ++j) {
+      const uint32_t e = (uint32_t)min(L * j + h, NDC - 1) * (uint32_t)N + ic;
+      dp[j] = ld_s(a_dyn_obs, e);
+      dgi[j] = ld_s(a_dyn_goal, e);
+    }
+#pragma unroll
+    for (int j = 0; j < SS; ++j) so[j] = ld_s(a_static_obs, (uint32_t)min(L * j + h, NSC - 1) * (uint32_t)N + ic);
   }
-#pragma unroll
-  for (int j = 0; j < SS; ++j) so[j] = ld_s(a_static_obs, (uint32_t)min(L * j + h, NSC - 1) * (uint32_t)N + ic);
   // (every load above goes through a preloaded argument; the ones below through KHot, the one
   // scalar load that the prologue waits for.  With no branch left in the prologue it is one
   // scheduling region: the two barriers keep the loads above in front of the wait for KHot -- the
@@ -1855,6 +1890,31 @@ __global__ __launch_bounds__(S2_CT, 2) void step2_kernel(const Tables* a_tables,
          a_dyn_goal, p.done, p.truncated, p.obs, p.obs_f32, p.status, p.pool};
 #pragma unroll
   for (int j = 0; j < TL; ++j) reinterpret_cast<uint4*>(&t_wave[w])[min(tt0 + j * TB, TW - 1)] = tword[j];
+  // WIDE: the rows into the wave's exchange area as loaded, 16 (4) contiguous bytes per lane; behind
+  // the wave barrier lane 2e + h reads its own slots back: rows 2j + h of env e.  Only this wave
+  // touches the area, and its LDS traffic runs in program order, so the tables' barrier below -- the
+  // fences that keep the compiler from reordering -- is all it needs.  (As lambdas: written out in
+  // place, the same statements compile to a read-back that is six instructions longer, with one
+  // address per dyn_goal byte; the A/B was run on this form.)
+  [[maybe_unused]] auto xchg_put = [&]() __attribute__((always_inline)) {
+    reinterpret_cast<uint4*>(stage + XL::XDYN)[lane] = xd;
+    reinterpret_cast<uint32_t*>(stage + XL::XGOAL)[lane] = xg;
+    reinterpret_cast<uint4*>(stage)[lane] = xs0;
+    reinterpret_cast<uint4*>(stage)[64 + lane] = xs1;
+  };
+  [[maybe_unused]] const uint32_t xe = ic - e0c;   // the env's place in the wave's rows (a wave past N: 31, env N - 1)
+  [[maybe_unused]] auto xchg_get = [&]() __attribute__((always_inline)) {
+#pragma unroll
+    for (int j = 0; j < SD; ++j) {
+      dp[j] = *reinterpret_cast<const int32_t*>(stage + XL::XDYN + (L * j + h) * XL::XROW + xe * 4u);
+      dgi[j] = stage[XL::XGOAL + (L * j + h) * 32 + xe];
+    }
+#pragma unroll
+    for (int j = 0; j < SS; ++j) so[j] = *reinterpret_cast<const int32_t*>(stage + (L * j + h) * XL::XROW + xe * 4u);
+  };
+  if constexpr (WIDE) {
+    xchg_put();
+  }
   // this wave's copy of the tables staged (state loads retire in order as used): a wave barrier, no
   // block barrier in the kernel -- 6.38-6.40 against 6.45-6.46 us with one block copy under a block
   // barrier (profiles/r04_step2_wave_tables_ab.txt; round 2 had measured the two the same)
@@ -1866,6 +1926,9 @@ __global__ __launch_bounds__(S2_CT, 2) void step2_kernel(const Tables* a_tables,
   if (DBG(DBG_WAIT_LOADS)) {   // diagnostics: when has every load of this wave landed?
     __builtin_amdgcn_s_waitcnt(0);
     DIAG(15);
+  }
+  if constexpr (WIDE) {
+    xchg_get();
   }
 
   // ---- this lane's dynamic obstacles: draws and moves first (no action needed; ballenv_env.py:323-353)
@@ -3698,6 +3761,8 @@ Launch pick_kernel(const be_config& c, int mode, bool fixed_ok, int lanes10, int
     L.kind = KIND_STEP2; L.consumes_pool = true;
     L.fn2 = pool ? step2_kernel<10, FIX_NS, FIX_ND, true> : step2_kernel<10, FIX_NS, FIX_ND, false>;
     L.fn2_recompute = pool ? step2_kernel<10, FIX_NS, FIX_ND, true, false> : step2_kernel<10, FIX_NS, FIX_ND, false, false>;
+    // (the name is the same: the row loads' width does not show in it, as PREVR does not)
+    L.fn2_wide = pool ? step2_kernel<10, FIX_NS, FIX_ND, true, true, true> : step2_kernel<10, FIX_NS, FIX_ND, false, true, true>;
     L.epb = S2_CT / 2; L.threads = S2_CT; L.lds = Step2Lds<10, FIX_NS, FIX_ND>::bytes;
     snprintf(L.name, sizeof L.name, "step2_kernel<10, %d, %d, %s>", FIX_NS, FIX_ND, pv);
     return L;
@@ -3800,10 +3865,10 @@ Launch pick_pool_fill(int window) {
   return L;
 }
 
-void launch_kernel(const Launch& L, const KParams& a, hipStream_t stream) {
+void launch_kernel(const Launch& L, const KParams& a, hipStream_t stream, bool wide) {
   const dim3 grid((unsigned)((a.n + L.epb - 1) / L.epb)), block((unsigned)L.threads);
   if (L.fn2)
-    hipLaunchKernelGGL(a.prev_read ? L.fn2 : L.fn2_recompute, grid, block, (size_t)L.lds, stream, a.tables, a.episode, a.ep_len, a.dyn_obs, a.dyn_goal,
+    hipLaunchKernelGGL(!a.prev_read ? L.fn2_recompute : (wide && L.fn2_wide ? L.fn2_wide : L.fn2), grid, block, (size_t)L.lds, stream, a.tables, a.episode, a.ep_len, a.dyn_obs, a.dyn_goal,
                        a.static_obs, a.n, a.gid0,
                        KHot{a.agent, a.goal, a.prev_dist, a.total_dist, a.ep_return, a.actions, a.stats, a.prev_read,
                             a.goal_change},

@@ -1,8 +1,9 @@
 // host_logic.h -- the host side's logic that needs no HIP: the autoreset pool's bookkeeping, the
-// checkpoint blob's layout, be_pool_entry's word order, the per-step slice of a be_out, be_mlp_rollout's
-// instance rule and argument checks.  Only
+// checkpoint blob's layout, be_pool_entry's word order, the per-step slice of a be_out, be_step's rule for
+// step2_kernel's wide-row-load instance, be_mlp_rollout's instance rule and argument checks.  Only
 // ballenv.h, pool_layout.h and standard headers, so the host C++ compiler alone builds and tests it
-// (tests/host_logic_main.cpp, tests/mlp_rollout_host_main.cpp); internal.h is the half that touches HIP.
+// (tests/host_logic_main.cpp, tests/step2_wide_host_main.cpp, tests/mlp_rollout_host_main.cpp); internal.h is
+// the half that touches HIP.
 #pragma once
 #include <stdint.h>
 #include <stdlib.h>
@@ -107,6 +108,29 @@ inline be_out be_out_at(const be_out& out, int64_t s, int64_t N, int64_t F) {
   if (o.final_len) o.final_len += s * N;
   return o;
 }
+
+// ---- be_step: does this call's state take step2_kernel's wide-row-load instance?  It loads a
+// wave's 32 envs of an obstacle row 16 bytes per lane, so every wave must be whole (num_envs a positive
+// multiple of 32) and every row chunk 16-byte aligned (the three obstacle arrays; with them aligned and
+// 32 | num_envs every row of every wave is).  force: BALLENV_STEP2_WIDE as be_create read it (-1: the rule;
+// 0: never; 1: wherever the instance is correct -- the conditions above are correctness, not preference,
+// and no override lifts them).  STEP2_WIDE_DEFAULT: what the rule answers without an override where the
+// instance may run.
+constexpr bool STEP2_WIDE_DEFAULT = true;
+inline bool step2_wide(int64_t num_envs, const void* static_obs, const void* dyn_obs, const void* dyn_goal, int force = -1) {
+  if (force == 0) return false;
+  if (num_envs < 32 || num_envs % 32) return false;
+  if (!static_obs || !dyn_obs || !dyn_goal) return false;
+  if (((uintptr_t)static_obs | (uintptr_t)dyn_obs | (uintptr_t)dyn_goal) & 15) return false;
+  return force == 1 || STEP2_WIDE_DEFAULT;
+}
+// BALLENV_STEP2_WIDE: exactly "0" or "1", else (or unset) -1
+inline int step2_wide_env(const char* v) {
+  if (!v || !v[0] || v[1]) return -1;
+  return v[0] == '0' ? 0 : (v[0] == '1' ? 1 : -1);
+}
+// which instance the context's last be_step / be_step_n launch took (be_step_instance, include/ballenv.h)
+enum { STEP_INSTANCE_NONE = 0, STEP_INSTANCE_PLAIN = 1, STEP_INSTANCE_WIDE = 2 };
 
 // ---- be_mlp_rollout: waves per workgroup of the fused kernel (mlp_rollout_kernel<LAYERS, NW>)
 // A wave owns 32 envs and a workgroup stages the whole packed image, which leaves room for one workgroup

@@ -144,6 +144,7 @@ struct Launch {
   KFn fn = nullptr;
   KFn2 fn2 = nullptr;            // step2_kernel (fn is nullptr then)
   KFn2 fn2_recompute = nullptr;  // its KParams::prev_read = 0 instance (A/B only; launch_kernel picks by the flag)
+  KFn2 fn2_wide = nullptr;       // its wide-row-load instance (be_step takes it per call: behost::step2_wide)
   KFnMlp fnm = nullptr;          // mlp_rollout_kernel (fn and fn2 are nullptr then; launch_mlp_rollout)
   int kind = KIND_NONE;
   int epb = BLOCK_THREADS;       // envs per block
@@ -176,7 +177,9 @@ BE_HIDDEN Launch pick_mlp_rollout(const be_config& c, bool fixed_ok, int layers,
 BE_HIDDEN void launch_mlp_rollout(const Launch& L, const KParams& a, const MlpRollParams& q, hipStream_t stream);
 BE_HIDDEN Launch pick_pool_fill(int window);   // window 10 or 5 (the kernels with consumes_pool)
 // The one place a step-engine kernel is launched: ceil(a.n / L.epb) blocks of L.threads, L.lds bytes.
-BE_HIDDEN void launch_kernel(const Launch& L, const KParams& a, hipStream_t stream);
+// wide: step2_kernel's wide-row-load instance (the caller has checked behost::step2_wide for a's arrays;
+// the prev_read = 0 A/B instance has no wide twin and ignores it).
+BE_HIDDEN void launch_kernel(const Launch& L, const KParams& a, hipStream_t stream, bool wide = false);
 BE_HIDDEN void launch_sample_actions(uint8_t* out, int32_t n, int32_t steps, int64_t env_offset, int32_t num_actions,
                                      unsigned long long seed, hipStream_t stream);
 

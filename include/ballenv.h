@@ -171,6 +171,13 @@ enum { BE_ENTRY_STEP_ACTIONS = 0,   /* be_step with caller action indices       
        BE_ENTRY_ROLLOUT = 2,        /* be_rollout (NULL when it falls back to looping be_step) */
        BE_ENTRY_RESET = 3, BE_ENTRY_OBSERVE = 4 };
 const char* be_kernel_name(const be_ctx* ctx, int32_t entry);
+/* Which instance of its kernel the context's last be_step / be_step_n call launched: 0 none yet,
+ * 1 the plain one, 2 step2_kernel's wide-row-load instance.  A state whose static_obs, dyn_obs and
+ * dyn_goal are 16-byte aligned, in a batch that is a multiple of 32 envs, takes the faster
+ * instance; anything else is still correct (bit for bit the same results) on the plain one.
+ * BALLENV_STEP2_WIDE=0 / 1, read at be_create, forces either side where it is valid (A/B).
+ * No GPU work.  Diagnostics only. */
+int32_t be_step_instance(const be_ctx* ctx);
 
 /* ---- device functions ---- */
 int be_create(const be_config* cfg, int32_t device, be_ctx** out);
