@@ -39,7 +39,8 @@ def __getattr__(name):
         from . import block_policy
         return getattr(block_policy, name)
     if name in ("PixelPolicy", "pixel_inputs", "HipPixelPolicy", "PixelRollout", "torch_pixel_forward",
-                "torch_pixel_select_action", "reference_pixel_weights"):
+                "torch_pixel_select_action", "reference_pixel_weights", "PixelGrad", "pixel_reinforce_losses",
+                "pixel_reinforce_update"):
         from . import pixel_policy
         return getattr(pixel_policy, name)
     if name == "BatchedBoard":
@@ -58,4 +59,5 @@ __all__ = ["EnvConfig", "MOVE_LIST", "step_bytes", "survey_step_bytes", "Box", "
            "torch_block_select_action", "reinforce_losses", "reinforce_update", "reference_block_weights",
            "BlockGrad", "supervised_losses", "supervised_update", "reference_supervise_data", "HipBlockOptim",
            "BlockTrainer", "SupervisedTrainer", "PixelPolicy", "pixel_inputs", "HipPixelPolicy", "PixelRollout",
-           "torch_pixel_forward", "torch_pixel_select_action", "reference_pixel_weights"]
+           "torch_pixel_forward", "torch_pixel_select_action", "reference_pixel_weights", "PixelGrad",
+           "pixel_reinforce_losses", "pixel_reinforce_update"]

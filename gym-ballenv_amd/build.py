@@ -41,6 +41,10 @@ object) and linked into one shared library:
                     per-env BatchNorm statistics) on be_observe_pixels' image (be_cnn_act); its host
                     half without HIP -- the packed image's layout and index function, the argument checks --
                     is csrc/cnn_host.h (CPU-tested)
+  csrc/cnn_grad.hip the pixel agent's REINFORCE loss and gradients of recorded rows (be_cnn_grad, DESIGN 3.20: f32
+                    MFMAs, the accumulators in the AGPR half as mlp_grad.hip's) and be_observe_quadrant; its host
+                    half without HIP -- the workspace's layout, the argument checks -- is csrc/cnn_grad_host.h
+                    (CPU-tested)
 """
 from __future__ import annotations
 
@@ -67,9 +71,9 @@ VGPR_MFMA = ["-mllvm", "-amdgpu-mfma-vgpr-form"]
 KARG_PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
 UNITS = {"ballenv.hip": [*VGPR_MFMA, *KARG_PRELOAD], "abi.hip": [], "policy.hip": ["-fno-slp-vectorize", *VGPR_MFMA],
          "features.hip": [], "pixels.hip": [], "board.hip": [], "a2c.hip": [], "a2c_grad.hip": [], "a2c_adam.hip": [],
-         "mlp_policy.hip": [], "mlp_grad.hip": [], "cnn_policy.hip": []}
+         "mlp_policy.hip": [], "mlp_grad.hip": [], "cnn_policy.hip": [], "cnn_grad.hip": []}
 HEADERS = [HDR, *(os.path.join(CSRC, h) for h in ("philox.h", "internal.h", "host_logic.h", "pool_layout.h", "policy_core.h", "blocks_core.h", "mlp_core.h", "diag.h",
-                                              "step_types.h", "optim_core.h", "pixels_host.h", "cnn_host.h"))]
+                                              "step_types.h", "optim_core.h", "pixels_host.h", "cnn_host.h", "cnn_grad_host.h"))]
 
 
 def _stale(out, deps):

@@ -224,13 +224,15 @@ class RowGrad:
     LOSS_WIDTH f64 ``_losses``; nothing is allocated per call, so a call can be graph-captured.  The weights
     are read from the module's parameters at call time (fp32, contiguous, on the env's device).
 
-    A subclass says what differs, as data: LOSS_WIDTH, WEIGHTS and GRADS (the ctypes structs: six tensor
-    pointers, unused ones NULL, then the network's sizes resp. the losses), and to ``__init__`` the parameters'
+    A subclass says what differs, as data: LOSS_WIDTH, WEIGHTS and GRADS (the ctypes structs: SLOTS tensor
+    pointers -- six unless the subclass says otherwise --, unused ones NULL, then the network's sizes resp. the
+    losses), and to ``__init__`` the parameters'
     names in the structs' order, the name of its ``*_workspace_bytes`` entry with that entry's sizes, and the
     sizes that end WEIGHTS.  Its ``__call__`` checks its rows (``_rows``), makes the C call on ``_params()``
     and ends in ``_ran``."""
 
     LOSS_WIDTH = 0
+    SLOTS = 6
     WEIGHTS = GRADS = None
 
     def __init__(self, env, policy, names, workspace_entry: str, workspace_sizes, sizes):
@@ -241,7 +243,7 @@ class RowGrad:
         if nbytes < 0:
             _abi.check(nbytes, env._ctx)
         self.workspace = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
-        self._names, self._sizes, self._pad = tuple(names), tuple(sizes), (None,) * (6 - len(names))
+        self._names, self._sizes, self._pad = tuple(names), tuple(sizes), (None,) * (self.SLOTS - len(names))
         sd = policy.state_dict()
         self.grads = {k: torch.zeros(sd[k].shape, dtype=torch.float32, device=dev) for k in self._names}
         self._losses = torch.zeros(self.LOSS_WIDTH, dtype=torch.float64, device=dev)

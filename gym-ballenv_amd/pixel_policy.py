@@ -18,6 +18,10 @@ The reference never calls ``policy.eval()`` and feeds one image at a time, so ev
 the HIP path).  ``norm="running"`` uses the stored running statistics, as ``PixelPolicy.eval()`` does.
 ``torch_pixel_forward`` / ``torch_pixel_select_action`` are both modes in plain PyTorch -- the numerics
 reference of the tests.
+``pixel_reinforce_losses`` / ``pixel_reinforce_update`` are the batched ``finish_episode`` (:98-117) over a
+recorded ``PixelRollout(record_images=True)``: gradients from torch autograd over the recorded images, or with
+grads="hip" from ``PixelGrad`` (``be_cnn_grad``, csrc/cnn_grad.hip: the loss and all 14 gradients straight from
+the u8 images, "sample" mode only -- the mode the reference trains in).
 """
 from __future__ import annotations
 
@@ -31,11 +35,17 @@ import torch.nn.functional as F
 
 from . import _abi
 from ._bind import HipHandle, categorical_pick, golden, want
-from .rollout import StepRollout
+from .block_policy import _episode_targets
+from .optim import RowGrad
+from .rollout import StepRollout, a2c_targets
 
 # be_cnn_act's work split (csrc/cnn_host.h): a persistent grid of one workgroup per compute unit, WAVES waves
 # each, a workgroup taking TILE envs per round (tile t of G workgroups: workgroup t % G, round t // G)
 TILE, WAVES = 4, 8
+# be_cnn_grad's (csrc/cnn_grad_host.h): a persistent grid of one workgroup per compute unit (at most
+# GRAD_MAX_SLOTS), GRAD_WAVES waves each, a workgroup taking GRAD_TILE rows per round (tile t of G workgroups:
+# workgroup t % G, round t // G)
+GRAD_TILE, GRAD_WAVES, GRAD_MAX_SLOTS = 2, 8, 1024
 IMAGE = (3, 40, 40)
 NORMS = {"sample": _abi.CNN_NORM_SAMPLE, "running": _abi.CNN_NORM_RUNNING}
 BN_EPS = 1e-5
@@ -175,13 +185,17 @@ class PixelRollout(StepRollout):
     """T steps of every env with the pixel policy in the loop (ball_cnn_reinforce.py's episode loop,
     batched): per step ``be_observe_pixels`` writes the images (with ``record_images`` into row t of
     ``images`` (T, N, 3, 40, 40) u8), ``be_cnn_act`` writes action and log_prob into row t, then
-    ``be_step`` writes rewards and dones into row t.  The loop, its (T, N) buffers, ``capture()`` and
-    ``run()`` are ``StepRollout``'s (rollout.py)."""
+    ``be_step`` writes rewards and dones into row t.  With ``record_images`` ``be_observe_quadrant`` also
+    writes the goal's quadrant into row t of ``quadrants`` (T, N) u8, which ``be_cnn_act`` then reads -- the
+    value it would compute itself, so the steps are the same bit for bit.  The loop, its (T, N) buffers,
+    ``capture()`` and ``run()`` are ``StepRollout``'s (rollout.py)."""
 
     def __init__(self, env, policy: PixelPolicy, horizon: int, norm: str = "sample", seed: int = 0,
                  record_images: bool = False):
         super().__init__(env, policy, HipPixelPolicy(env, policy, norm=norm, seed=int(seed)), horizon, seed)
         self.images = torch.zeros(self.T, env.num_envs, *IMAGE, dtype=torch.uint8, device=env.device) \
+            if record_images else None
+        self.quadrants = torch.zeros(self.T, env.num_envs, dtype=torch.uint8, device=env.device) \
             if record_images else None
 
     def _act(self, t: int, s) -> None:
@@ -191,7 +205,140 @@ class PixelRollout(StepRollout):
         rc = lib.be_observe_pixels(env._ctx, C.byref(env._st), None, img, None, s)
         if rc:
             _abi.check(rc, env._ctx)
-        rc = lib.be_cnn_act(self.hp._h, C.byref(env._st), img, None, NORMS[self.hp.norm],
+        quad = None
+        if self.quadrants is not None:
+            quad = self.quadrants[t].data_ptr()
+            rc = lib.be_observe_quadrant(env._ctx, C.byref(env._st), quad, s)
+            if rc:
+                _abi.check(rc, env._ctx)
+        rc = lib.be_cnn_act(self.hp._h, C.byref(env._st), img, quad, NORMS[self.hp.norm],
                             C.byref(self._act_outs[t]), self.seed & (2**64 - 1), s)
         if rc:
             _abi.check(rc, env._ctx)
+
+
+class PixelGrad(RowGrad):
+    """``be_cnn_grad`` bound to one BatchedBallEnv and one PixelPolicy: the loss sum of
+    ``pixel_reinforce_losses`` and what ``loss.backward()`` leaves in each of the 14 ``.grad``, from the
+    recorded u8 images in three launches ("sample" mode: each image's own BatchNorm statistics; the conv
+    biases' gradients are exact zeros there).  The workspace, the gradient tensors (``.grads``), the checks of
+    the weights and ``assign()``: ``RowGrad`` (optim.py); ``.losses`` is its f64 pair (scale * the sum of the
+    row losses, the number of active rows)."""
+
+    LOSS_WIDTH = 2
+    SLOTS = len(_abi.CNN_PARAMS)
+    WEIGHTS, GRADS = _abi.BeCnnWeights, _abi.BeCnnGrads
+
+    def __init__(self, env, policy: PixelPolicy):
+        self.num_actions = int(policy.head.out_features)
+        super().__init__(env, policy, _abi.CNN_PARAMS, "be_cnn_grad_workspace_bytes", (self.num_actions,), ())
+        self.losses = self._losses
+
+    def _params(self):
+        """The module's 14 parameters, checked, and their be_cnn_weights (the running statistics NULL)."""
+        ps, dev = dict(self.policy.named_parameters()), self.env.device
+        if ps.keys() != set(self._names):
+            raise ValueError("PixelGrad needs a PixelPolicy module")
+        ws = {k: want(ps[k].detach(), f"policy parameter {k}", torch.float32, tuple(self.grads[k].shape), dev)
+              for k in self._names}
+        return list(ws.values()), self.WEIGHTS(*(ws[k].data_ptr() if k in ws else None for k in _abi.CNN_TENSORS))
+
+    def __call__(self, images: torch.Tensor, quadrants: torch.Tensor, actions: torch.Tensor,
+                 coef: Optional[torch.Tensor] = None, valid: Optional[torch.Tensor] = None, scale: float = 1.0,
+                 probs: Optional[torch.Tensor] = None):
+        """images (T, N, 3, 40, 40) or (rows, 3, 40, 40) u8; quadrants u8 in 0..3, actions u8, coef f32 or None
+        (= 1), valid u8 / bool or None (= every row), each (T, N) or (rows,); probs: an f32 tensor of that
+        leading shape + (A,) that receives the forward's probabilities, or None: contiguous, on the env's
+        device.  Asynchronous on the caller's current stream.  Returns ``.grads``."""
+        dev = self.env.device
+        lead = (None, None) if isinstance(images, torch.Tensor) and images.dim() == 5 else (None,)
+        lead = tuple(want(images, "images", torch.uint8, (*lead, *IMAGE), dev).shape[:-3])
+        want(quadrants, "quadrants", torch.uint8, lead, dev)
+        want(actions, "actions", torch.uint8, lead, dev)
+        want(coef, "coef", torch.float32, lead, dev, optional=True)
+        want(valid, "valid", (torch.bool, torch.uint8), lead, dev, optional=True)
+        want(probs, "probs", torch.float32, (*lead, self.num_actions), dev, optional=True)
+        rows = 1
+        for n in lead:
+            rows *= int(n)
+        ws, w = self._params()
+        g = self._g
+        if probs is not None:
+            g = self.GRADS(*(self.grads[k].data_ptr() for k in self._names), self._losses.data_ptr(), probs.data_ptr())
+        rc = self._lib.be_cnn_grad(self.env._ctx, images.data_ptr(), quadrants.data_ptr(), actions.data_ptr(),
+                                   None if coef is None else coef.data_ptr(),
+                                   None if valid is None else valid.data_ptr(), rows, float(scale), C.byref(w),
+                                   self.num_actions, self.workspace.data_ptr(), self.workspace.numel() * 8,
+                                   C.byref(g), self.env._stream())
+        return self._ran(rc, ws)
+
+
+def pixel_reinforce_losses(policy: PixelPolicy, images: torch.Tensor, quadrants: torch.Tensor, actions: torch.Tensor,
+                           rewards: torch.Tensor, dones: torch.Tensor, gamma: float = 0.99, targets=None) -> torch.Tensor:
+    """Batched ``finish_episode`` (examples/ball_cnn_reinforce.py:98-117) over a recorded rollout:
+    ``block_policy.reinforce_losses`` for this network, in plain torch.
+
+    images (T, N, 3, 40, 40) u8 and quadrants (T, N) u8 -- what each action was drawn from; actions (T, N);
+    rewards (T, N) f64; dones (T, N) bool.  Every maximal run of an env's steps that ends at a done (or at the
+    horizon) is one episode; per episode R_t = r_t + gamma R_{t+1}, torch.tensor(R) (fp32),
+    R^ = (R - R.mean()) / (R.std() + eps), loss = sum_t -log pi(a_t|s_t) R^_t; episodes of one step are left
+    out.  log pi is recomputed with autograd: ``torch_pixel_forward(norm="sample")`` in the module's own
+    precision, then ``Categorical(probs).log_prob``.  Returns the loss summed over all episodes (f64).
+    targets: ``(returns_norm, valid)``, both (T, N), from ``a2c_targets(env, rewards, dones, None, gamma)``."""
+    T, N = rewards.shape
+    if targets is None:
+        Rn, valid = _episode_targets(rewards, dones, gamma, float(np.finfo(np.float32).eps))
+    else:
+        Rn, valid = targets[0], targets[1]
+        if tuple(Rn.shape) != (T, N) or tuple(valid.shape) != (T, N):
+            raise ValueError("targets must be (returns_norm, valid), both (T, N)")
+        Rn, valid = Rn.reshape(-1), valid.reshape(-1).to(torch.bool)
+    dtype = policy.conv1.weight.dtype
+    x = images.reshape(T * N, *IMAGE).to(dtype) / 255.0
+    q = F.one_hot(quadrants.reshape(-1).long(), 4).to(dtype)
+    probs = torch_pixel_forward(policy, x, q, "sample")
+    logp = torch.distributions.Categorical(probs=probs).log_prob(actions.reshape(-1).long())
+    return -(logp.double() * Rn.double())[valid].sum()      # products and sum in f64: no rounding of its own
+
+
+def pixel_reinforce_update(rollout: PixelRollout, optimizer, gamma: float = 0.99, targets: str = "hip",
+                           grads: str = "torch") -> float:
+    """One REINFORCE step on a recorded rollout (record_images=True, norm="sample"): the targets
+    (targets="hip": ``be_a2c_targets`` with no values; "torch": ``pixel_reinforce_losses``' own),
+    loss.backward(), optimizer.step(), then the new weights re-packed for the HIP kernel
+    (``rollout.hp.load``).  Returns the loss value.  grads: "torch" (``pixel_reinforce_losses`` + autograd)
+    or "hip" (``PixelGrad``, cached on the rollout: the loss and every .grad from ``be_cnn_grad``, no autograd
+    graph and no f32 copy of the images; needs targets="hip").  optimizer: a torch optimiser over
+    ``rollout.policy.parameters()``."""
+    if rollout.images is None:
+        raise ValueError("pixel_reinforce_update needs PixelRollout(record_images=True)")
+    if rollout.hp.norm != "sample":
+        raise ValueError("pixel_reinforce_update needs a PixelRollout with norm='sample' (the mode the reference trains in)")
+    if targets not in ("torch", "hip"):
+        raise ValueError("targets must be 'torch' or 'hip'")
+    if grads not in ("torch", "hip"):
+        raise ValueError("grads must be 'torch' or 'hip'")
+    if grads == "hip":
+        if targets != "hip":
+            raise ValueError("grads='hip' needs targets='hip'")
+        t = a2c_targets(rollout.env, rollout.rewards, rollout.dones, None, gamma, with_returns=False)
+        pg = getattr(rollout, "_pixel_grad", None)
+        if pg is None or pg.policy is not rollout.policy:
+            pg = rollout._pixel_grad = PixelGrad(rollout.env, rollout.policy)
+        pg(rollout.images, rollout.quadrants, rollout.actions, t.returns_norm, t.valid, scale=1.0)
+        pg.assign()
+        loss = float(pg.losses[0])
+        optimizer.step()
+        rollout.hp.load(rollout.policy)
+        return loss
+    tg = None
+    if targets == "hip":
+        t = a2c_targets(rollout.env, rollout.rewards, rollout.dones, None, gamma, with_returns=False)
+        tg = (t.returns_norm, t.valid)
+    loss = pixel_reinforce_losses(rollout.policy, rollout.images, rollout.quadrants, rollout.actions, rollout.rewards,
+                                  rollout.dones, gamma, targets=tg)
+    optimizer.zero_grad()
+    loss.backward()
+    optimizer.step()
+    rollout.hp.load(rollout.policy)
+    return float(loss.detach())

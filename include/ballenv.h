@@ -471,6 +471,58 @@ int be_cnn_act(be_cnn* cnn, const be_state* st, const uint8_t* image, const uint
 /* Bytes of the packed weight image. */
 int64_t be_cnn_bytes(const be_cnn* cnn);
 
+/* ---- the pixel agent's loss and gradients: finish_episode of examples/ball_cnn_reinforce.py:98-117 ----
+ * The REINFORCE loss of the network above over `rows` recorded rows (every row offset is 64-bit) and its
+ * gradients, i.e. what loss.backward() leaves in each .grad; be_mlp_grad's contract (below) for this
+ * network.  Contiguous device arrays: images (rows, 3, 40, 40) u8, 16-byte aligned; quadrants (rows) u8 in
+ * 0..3; actions (rows) u8; coef (rows) f32 or NULL (= 1); valid (rows) u8 or NULL (= every row).  The
+ * BatchNorm mode is BE_CNN_NORM_SAMPLE, the only one the reference trains in: weights' running statistics
+ * are not read and may be NULL.  A row is active when it is valid and action < num_actions; any other row
+ * adds exactly +0.  Per row, in f32 (a = its action, c = its coef, eps = FLT_EPSILON):
+ *   forward  be_cnn_act's pinned arithmetic above: grads->probs of a row, if given, are bit for bit the
+ *            probs be_cnn_act writes for that image and quadrant
+ *   loss     += -c * log(min(max(p_a, eps), 1 - eps))          (Categorical(probs).log_prob's clamp)
+ *   dz_j     = c * (p_j - [j == a]) if eps <= p_a <= 1 - eps, else 0; p_a - 1 is taken as -(sum of the
+ *            other p_j, added in action order): the same number without the cancellation where p_a is near 1
+ *   head     gW_head += dz (x) [flatten(y3), one_hot(quadrant)];  gb_head += dz;  dy3 = W_head[:, :128]^T dz
+ *   each BatchNorm layer, per map of n = 4, 49, 324 positions, xhat = (conv - mean) * inv:
+ *            dyr = (xhat * gamma + beta > 0) ? dy : 0   (the forward's own expression: the same mask)
+ *            gbeta += sum dyr;  ggamma += sum dyr * xhat   (the sums as the forward's statistics:
+ *            interleaved partials combined pairwise)
+ *            dconv = (gamma * inv) * ((dyr - (sum dyr) / n) - xhat * ((sum dyr * xhat) / n))
+ *   each convolution:  gW[co][ci][ky][kx] += sum_pos dconv[co][pos] * in[ci][2 oy + ky][2 ox + kx];
+ *            din = the matching transposed convolution (none for the image)
+ *   conv1..3_bias: the per-map mean subtracts the bias, so its gradient is zero: written as exact +0
+ * Every product with more than a handful of terms is an f32 fma chain on v_mfma_f32_16x16x4_f32
+ * (csrc/cnn_grad.hip has the operand and chain order).  No float atomics: each workgroup of a grid that
+ * depends only on rows and the device adds its rows in a fixed order and writes its sums to `workspace`; a
+ * last kernel adds the workgroups' sums in workgroup order in f64, multiplies by `scale` in f64 and rounds
+ * once to f32.  losses[0] is scale * the f64 sum of the row losses, losses[1] the number of active rows.
+ * Two calls on the same inputs and device give the same bits whatever the workspace held, and a row's
+ * contribution does not depend on its place among the rows.  Every output element is written on every call
+ * (zeros when no row is active; rows = 0 is valid).  Asynchronous on `stream`, no allocation and no
+ * synchronisation (graph-capturable).  BE_E_INVALID, with the argument named in be_last_error and nothing
+ * launched: a NULL ctx or required pointer, a misaligned images, num_actions outside [1, 15], rows < 0, a
+ * workspace that is too small (or not 16-byte aligned).                                          */
+typedef struct be_cnn_grads {       /* what loss.backward() leaves in each .grad; state_dict shapes */
+  float *conv1_weight, *conv1_bias, *bn1_weight, *bn1_bias,
+        *conv2_weight, *conv2_bias, *bn2_weight, *bn2_bias,
+        *conv3_weight, *conv3_bias, *bn3_weight, *bn3_bias, *head_weight, *head_bias;
+  double* losses;                   /* [2]: scale * f64 sum of the row losses, number of active rows */
+  float*  probs;                    /* optional (rows, A): the forward's probabilities               */
+} be_cnn_grads;
+/* Bytes of workspace be_cnn_grad needs on ctx's device (16-byte aligned; independent of rows);
+ * < 0: an error code.                                                                       */
+int64_t be_cnn_grad_workspace_bytes(be_ctx* ctx, int32_t num_actions);
+int be_cnn_grad(be_ctx* ctx, const uint8_t* images, const uint8_t* quadrants, const uint8_t* actions,
+                const float* coef, const uint8_t* valid, int64_t rows, double scale,
+                const be_cnn_weights* weights, int32_t num_actions,
+                void* workspace, int64_t workspace_bytes, const be_cnn_grads* grads, void* stream);
+/* The goal's quadrant of every env of st, out (N) u8 in 0..3: prep_state2's rule, the index of the one set
+ * byte among be_observe_blocks' first four -- what be_cnn_act computes itself when quadrant_in is NULL.
+ * One launch, asynchronous on stream, graph-capturable.                                            */
+int be_observe_quadrant(be_ctx* ctx, const be_state* st, uint8_t* out, void* stream);
+
 /* ---- the block-count MLP's losses and gradients: both of the reference's training loops ----
  *   finish_episode       examples/ball_env_reinforce.py:88-108  sum of -Categorical(probs).log_prob(a) * R^
  *   the supervised loop  examples/train_supervise.py:66-101     mean CrossEntropyLoss on the logits
