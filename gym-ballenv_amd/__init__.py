@@ -40,7 +40,7 @@ def __getattr__(name):
         return getattr(block_policy, name)
     if name in ("PixelPolicy", "pixel_inputs", "HipPixelPolicy", "PixelRollout", "torch_pixel_forward",
                 "torch_pixel_select_action", "reference_pixel_weights", "PixelGrad", "pixel_reinforce_losses",
-                "pixel_reinforce_update"):
+                "pixel_reinforce_update", "HipPixelAdam", "PixelTrainer"):
         from . import pixel_policy
         return getattr(pixel_policy, name)
     if name == "BatchedBoard":
@@ -60,4 +60,4 @@ __all__ = ["EnvConfig", "MOVE_LIST", "step_bytes", "survey_step_bytes", "Box", "
            "BlockGrad", "supervised_losses", "supervised_update", "reference_supervise_data", "HipBlockOptim",
            "BlockTrainer", "SupervisedTrainer", "PixelPolicy", "pixel_inputs", "HipPixelPolicy", "PixelRollout",
            "torch_pixel_forward", "torch_pixel_select_action", "reference_pixel_weights", "PixelGrad",
-           "pixel_reinforce_losses", "pixel_reinforce_update"]
+           "pixel_reinforce_losses", "pixel_reinforce_update", "HipPixelAdam", "PixelTrainer"]

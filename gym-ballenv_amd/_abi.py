@@ -32,7 +32,7 @@ EXPORTS = ("be_abi_version", "be_config_default", "be_config_check", "be_step_by
            "be_mlp_rollout", "be_mlp_rollout_kernel",
            "be_mlp_grad_workspace_bytes", "be_mlp_grad", "be_mlp_opt",
            "be_cnn_create", "be_cnn_destroy", "be_cnn_load", "be_cnn_act", "be_cnn_bytes",
-           "be_cnn_grad_workspace_bytes", "be_cnn_grad", "be_observe_quadrant",
+           "be_cnn_grad_workspace_bytes", "be_cnn_grad", "be_observe_quadrant", "be_cnn_adam",
            "be_board_config_default", "be_board_create", "be_board_destroy", "be_board_last_error",
            "be_board_reset", "be_board_step", "be_board_rollout", "be_board_observe", "be_board_status",
            "be_board_pool_bytes")
@@ -133,6 +133,10 @@ CNN_PARAMS = tuple(k for k in CNN_TENSORS if "running" not in k)
 
 class BeCnnGrads(C.Structure):
     _fields_ = [(k.replace(".", "_"), C.c_void_p) for k in CNN_PARAMS] + [("losses", C.c_void_p), ("probs", C.c_void_p)]
+
+
+class BeCnnTensors(C.Structure):
+    _fields_ = [(k.replace(".", "_"), C.c_void_p) for k in CNN_PARAMS]
 
 
 class BeA2CTensors(C.Structure):
@@ -240,6 +244,8 @@ def lib() -> C.CDLL:
         "be_cnn_grad": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, C.c_double, P(BeCnnWeights), i32, vp, i64,
                                   P(BeCnnGrads), vp]),
         "be_observe_quadrant": (C.c_int, [vp, P(BeState), vp, vp]),
+        "be_cnn_adam": (C.c_int, [vp, P(BeCnnTensors), P(BeCnnTensors), P(BeCnnTensors), P(BeCnnTensors), vp,
+                                  C.c_double, C.c_double, C.c_double, vp, vp, i32, vp]),
         "be_a2c_targets": (C.c_int, [vp, vp, vp, vp, vp, i32, C.c_double, C.c_double, P(BeA2COut), vp]),
         "be_a2c_grad_workspace_bytes": (i64, [vp, i32, i32]),
         "be_a2c_grad": (C.c_int, [vp, vp, vp, vp, vp, i64, P(BeA2CWeights), vp, i64, P(BeA2CGrads), vp]),

@@ -25,7 +25,7 @@ object) and linked into one shared library:
   csrc/optim_core.h the pinned optimiser arithmetic, once: an Adam step's constants, one element's Adam
                     and SGD update (f64 operations with -ffp-contract=off, as every unit: no FMA)
   csrc/a2c_adam.hip the Adam step on the six Policy tensors and the re-pack of the policy image
-                    (optim_core.h); and the one-thread state kernel both optimiser entries launch
+                    (optim_core.h); and the one-thread state kernel all three optimiser entries launch
   csrc/mlp_policy.hip select_action of the REINFORCE / supervised block-count MLP (f32 MFMAs) straight
                     from the env state; shares blocks_core.h (prep_state2 of one env) with features.hip;
                     and next to its pack kernel the Adam / SGD step fused with the re-pack (be_mlp_opt,
@@ -38,9 +38,10 @@ object) and linked into one shared library:
                     (f32 MFMAs; no VGPR_MFMA, for a2c_grad.hip's reason: the gradient accumulators live
                     for the whole kernel, the AGPR half of the register file is where they belong)
   csrc/cnn_policy.hip select_action of the pixel agent's conv net (f32 MFMAs as implicit GEMMs, the reference's
-                    per-env BatchNorm statistics) on be_observe_pixels' image (be_cnn_act); its host
-                    half without HIP -- the packed image's layout and index function, the argument checks --
-                    is csrc/cnn_host.h (CPU-tested)
+                    per-env BatchNorm statistics) on be_observe_pixels' image (be_cnn_act), and next
+                    to its pack kernel the Adam step fused with the re-pack (be_cnn_adam, optim_core.h, DESIGN
+                    3.21); its host half without HIP -- the packed image's layout, its index function and that
+                    function's inverse, the argument checks -- is csrc/cnn_host.h (CPU-tested)
   csrc/cnn_grad.hip the pixel agent's REINFORCE loss and gradients of recorded rows (be_cnn_grad, DESIGN 3.20: f32
                     MFMAs, the accumulators in the AGPR half as mlp_grad.hip's) and be_observe_quadrant; its host
                     half without HIP -- the workspace's layout, the argument checks -- is csrc/cnn_grad_host.h

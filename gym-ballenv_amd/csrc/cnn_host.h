@@ -1,8 +1,9 @@
 // cnn_host.h -- be_cnn_*'s host side that needs no HIP (pixels_host.h's and host_logic.h's sibling):
-// the pixel agent's network shape, the packed weight image's layout and its index function, and the
-// entries' argument checks.  Only ballenv.h and standard headers, so the host C++ compiler alone
-// builds and tests it (tests/cnn_host_main.cpp); the layout functions are constexpr, so the kernels
-// of cnn_policy.hip use the same text.
+// the pixel agent's network shape, the packed weight image's layout, its index function and that
+// function's inverse (be_cnn_adam's scatter), and the entries' argument checks.  Only ballenv.h and
+// standard headers, so the host C++ compiler alone builds and tests it (tests/cnn_host_main.cpp,
+// tests/cnn_adam_host_main.cpp); the layout functions are constexpr, so the kernels of cnn_policy.hip
+// use the same text.
 #pragma once
 #include <stdint.h>
 
@@ -118,6 +119,57 @@ constexpr int cnn_pack_source(int i, int A, int* elem) {
   return third ? CT_CONV3_W : CT_CONV2_W;
 }
 
+// be_cnn_tensors' fields in order: the 14 parameters, be_cnn_weights without the six running statistics.
+constexpr int CNN_PARAMS = 14;
+constexpr const char* const CNN_PARAM_NAMES[CNN_PARAMS] = {
+    "conv1_weight", "conv1_bias", "bn1_weight", "bn1_bias", "conv2_weight", "conv2_bias", "bn2_weight", "bn2_bias",
+    "conv3_weight", "conv3_bias", "bn3_weight", "bn3_bias", "head_weight", "head_bias"};
+// parameter k's CnnTensor id: four per layer, then the head's two
+constexpr int cnn_param_tensor(int k) { return k < 12 ? 6 * (k >> 2) + (k & 3) : k + 6; }
+// Element i of the 14 parameters laid end to end in that order: its parameter, *elem its flat state_dict
+// index; -1 behind the last.  Compares against the running ends, which but for the head's are constants.
+constexpr int cnn_param_at(int i, int A, int* elem) {
+  int k = -1, lo = 0, end = 0;
+  for (int q = 0; q < CNN_PARAMS; ++q) {
+    const int next = end + cnn_tensor_elems(cnn_param_tensor(q), A);
+    const bool in = i >= end && i < next;
+    k = in ? q : k;
+    lo = in ? end : lo;
+    end = next;
+  }
+  *elem = i - lo;
+  return k;
+}
+constexpr int cnn_param_elems(int A) {
+  int n = 0;
+  for (int q = 0; q < CNN_PARAMS; ++q) n += cnn_tensor_elems(cnn_param_tensor(q), A);
+  return n;
+}
+// cnn_pack_source inverted: the one image index that holds element elem of tensor t (a CnnTensor id), as
+// be_cnn_adam's update kernel scatters it; -1 for a running statistic, which is no parameter.
+constexpr int cnn_pack_dest(int t, int elem) {
+  if (t == CT_CONV1_W) {
+    const int m = elem / (CNN_C0 * CNN_TAPS), r = elem % (CNN_C0 * CNN_TAPS);
+    const int j = r / CNN_KS, kx = r % CNN_KS;              // j = 5 ci + ky
+    const int s = kx < 4 ? j : 15 + j / 4, l4 = kx < 4 ? kx : j % 4;
+    return CNN_F1 + s * 64 + l4 * 16 + m;
+  }
+  if (t == CT_CONV2_W || t == CT_CONV3_W) {
+    const int cin = t == CT_CONV2_W ? CNN_C1 : CNN_C2;
+    const int tap = elem % CNN_TAPS, mc = elem / CNN_TAPS, ci = mc % cin, m = mc / cin;
+    const int s = CNN_TAPS * (ci / 4) + tap;
+    return (t == CT_CONV2_W ? CNN_F2 : CNN_F3) + (2 * s + m / 16) * 64 + (ci % 4) * 16 + m % 16;
+  }
+  if (t == CT_HEAD_W) {
+    const int m = elem / CNN_HEAD_IN, k = elem % CNN_HEAD_IN;
+    return CNN_FH + (k / 4) * 64 + (k % 4) * 16 + m;
+  }
+  if (t == CT_HEAD_B) return CNN_HBIAS + elem;
+  const int layer = t / 6, row = t % 6 - 1;                 // row 0 the conv bias, 1 gamma, 2 beta
+  if (row > 2) return -1;
+  return (layer == 0 ? CNN_P1 : (layer == 1 ? CNN_P2 : CNN_P3)) + row * (layer == 0 ? CNN_C1 : CNN_C2) + elem;
+}
+
 // The act kernel's LDS (offsets in floats behind the staged image part)
 constexpr int CNN_L_LUT = CNN_STAGED;                          // [256] v / 255.0f
 constexpr int CNN_L_A1 = CNN_L_LUT + 256;                      // [TILE][16][324] conv1, then y1 in place
@@ -157,6 +209,29 @@ inline const char* cnn_act_args_error(const void* image, int32_t norm, const be_
   if (!out || !out->action) return "be_cnn_act needs out->action";
   if (out->value) return "be_cnn_act: out->value must be NULL (this network has no value head)";
   return nullptr;
+}
+// the first of a set's 14 pointers that is NULL or not 4-byte aligned, as an index, or -1
+inline int cnn_bad_param(const be_cnn_tensors* t) {
+  const float* const p[CNN_PARAMS] = {
+      t->conv1_weight, t->conv1_bias, t->bn1_weight, t->bn1_bias, t->conv2_weight, t->conv2_bias, t->bn2_weight,
+      t->bn2_bias, t->conv3_weight, t->conv3_bias, t->bn3_weight, t->bn3_bias, t->head_weight, t->head_bias};
+  for (int i = 0; i < CNN_PARAMS; ++i)
+    if (!p[i] || ((uintptr_t)p[i] & 3)) return i;
+  return -1;
+}
+// be_cnn_adam's four tensor sets, checked in this order (every set before any tensor).  false: fine; else
+// *set names the set and *field the tensor ("grads", "conv2_weight"), or is NULL where the set itself is NULL.
+inline bool cnn_adam_sets_error(const be_cnn_tensors* params, const be_cnn_tensors* grads, const be_cnn_tensors* exp_avg,
+                                const be_cnn_tensors* exp_avg_sq, const char** set, const char** field) {
+  const be_cnn_tensors* const sets[4] = {params, grads, exp_avg, exp_avg_sq};
+  const char* const names[4] = {"params", "grads", "exp_avg", "exp_avg_sq"};
+  for (int s = 0; s < 4; ++s)
+    if (!sets[s]) { *set = names[s]; *field = nullptr; return true; }
+  for (int s = 0; s < 4; ++s) {
+    const int bad = cnn_bad_param(sets[s]);
+    if (bad >= 0) { *set = names[s]; *field = CNN_PARAM_NAMES[bad]; return true; }
+  }
+  return false;
 }
 
 }  // namespace behost

@@ -10,6 +10,9 @@
 //
 //   be_cnn_load   one launch: the 20 f32 state_dict arrays into the packed image (cnn_host.h)
 //   be_cnn_act    one launch: the forward, softmax and draw, the arithmetic include/ballenv.h pins
+//   be_cnn_adam   two launches: optimizer.step() (Adam, ball_cnn_reinforce.py:115, :244) on the 14 parameters
+//                 fused with the re-pack of the image, then the state kernel shared with
+//                 be_a2c_adam and be_mlp_opt (be_internal_optim_advance)
 //
 // Every product runs on v_mfma_f32_16x16x4_f32 (an exact f32 fma chain) as an implicit GEMM
 // D = W . patches: the weights are the A operand (row = output channel), a column of the B operand is
@@ -48,8 +51,10 @@
 
 #include "ballenv.h"
 #include "cnn_host.h"
+#include "host_logic.h"
 #include "internal.h"
 #include "mlp_core.h"
+#include "optim_core.h"
 #include "philox.h"
 #include "policy_core.h"
 
@@ -80,6 +85,44 @@ __global__ __launch_bounds__(256) void cnn_pack_kernel(CPack a, float* img) {
     }
     img[i] = v;
   }
+}
+
+// be_cnn_adam: the Adam step on the 14 parameters and the pack above, inverted.  Thread i takes source
+// element i of the parameters laid end to end in be_cnn_tensors' order (cnn_param_at), so a wave reads
+// w, g, m, v and writes w, m, v as consecutive floats, and scatters its new weight to the one image index
+// that cnn_pack_kernel fills from that element (cnn_pack_dest).  The map is a bijection onto the image's
+// entries that hold a parameter (tests/cnn_adam_host_main.cpp): no element has two writers and no thread
+// reads what another writes.  The running statistics' rows, the pads and hb keep what be_cnn_load wrote.
+struct CSet { float* t[CNN_PARAMS]; };
+
+struct CAdam {
+  CSet w, g, m, v;           // params, grads (read only), exp_avg, exp_avg_sq
+  const double* state;       // [t, beta1^t, beta2^t, lr] before the call
+  double beta1, beta2, eps;
+  float* img;
+  int32_t A;
+};
+
+__global__ __launch_bounds__(256) void cnn_adam_kernel(CAdam p) {
+  int j;
+  const int k = cnn_param_at((int)(blockIdx.x * 256 + threadIdx.x), p.A, &j);
+  if (k < 0) return;
+  float *w = p.w.t[0], *m1p = p.m.t[0], *m2p = p.v.t[0];
+  const float* g = p.g.t[0];
+#pragma unroll
+  for (int q = 1; q < CNN_PARAMS; ++q) {                     // selects: no indexed copy of the tables
+    w = k == q ? p.w.t[q] : w;
+    g = k == q ? p.g.t[q] : g;
+    m1p = k == q ? p.m.t[q] : m1p;
+    m2p = k == q ? p.v.t[q] : m2p;
+  }
+  // the pinned arithmetic of include/ballenv.h (optim_core.h)
+  p.img[cnn_pack_dest(cnn_param_tensor(k), j)] = adam_elem(adam_step(p.state, p.beta1, p.beta2, p.eps), g, m1p, m2p, w, j);
+}
+
+CSet cnn_set(const be_cnn_tensors* t) {
+  return CSet{{t->conv1_weight, t->conv1_bias, t->bn1_weight, t->bn1_bias, t->conv2_weight, t->conv2_bias, t->bn2_weight,
+               t->bn2_bias, t->conv3_weight, t->conv3_bias, t->bn3_weight, t->bn3_bias, t->head_weight, t->head_bias}};
 }
 
 struct CParams {
@@ -441,6 +484,33 @@ int be_cnn_act(be_cnn* m, const be_state* st, const uint8_t* image, const uint8_
   const dim3 grid((unsigned)(p.ntiles < m->cus ? p.ntiles : m->cus)), block(CNN_THREADS);
   hipLaunchKernelGGL(cnn_act_kernel, grid, block, (size_t)CNN_LDS_BYTES, (hipStream_t)stream, p);
   return be_launched(be_ctx_err(ctx));
+}
+
+int be_cnn_adam(be_cnn* m, const be_cnn_tensors* params, const be_cnn_tensors* grads, const be_cnn_tensors* exp_avg,
+                const be_cnn_tensors* exp_avg_sq, double* state, double beta1, double beta2, double eps,
+                const double* losses, double* loss_log, int32_t log_rows, void* stream) {
+  if (!m) return be_ctx_fail(nullptr, BE_E_INVALID, "be_cnn_adam: cnn is NULL");
+  be_ctx* ctx = m->ctx;
+  char* err = be_ctx_err(ctx);
+  if (!m->loaded) return be_ctx_fail(ctx, BE_E_INVALID, "be_cnn_adam before be_cnn_load");
+  const char *set, *field;
+  if (behost::cnn_adam_sets_error(params, grads, exp_avg, exp_avg_sq, &set, &field)) {
+    if (!field) return be_fail(err, BE_E_INVALID, "be_cnn_adam: %s is NULL", set);
+    char name[64];
+    snprintf(name, sizeof name, "%s->%s", set, field);
+    return be_fail(err, BE_E_INVALID, "be_cnn_adam: %s is NULL or not 4-byte aligned", name);
+  }
+  if (const char* msg = behost::optim_args_error(state, true, beta1, beta2, eps, losses, loss_log, log_rows))
+    return be_fail(err, BE_E_INVALID, "be_cnn_adam: %s", msg);
+  BE_ENTER_DEVICE(err, m->cv.device);
+  CAdam p{};
+  p.w = cnn_set(params); p.g = cnn_set(grads); p.m = cnn_set(exp_avg); p.v = cnn_set(exp_avg_sq);
+  p.state = state; p.beta1 = beta1; p.beta2 = beta2; p.eps = eps;
+  p.img = m->img; p.A = m->A;
+  const dim3 grid((unsigned)((cnn_param_elems(m->A) + 255) / 256)), block(256);
+  hipLaunchKernelGGL(cnn_adam_kernel, grid, block, 0, (hipStream_t)stream, p);
+  if (int rc = be_launched(err)) return rc;
+  return be_internal_optim_advance(err, state, true, beta1, beta2, losses, loss_log, 2, log_rows, stream);
 }
 
 int64_t be_cnn_bytes(const be_cnn* m) { return m ? (int64_t)CNN_TOTAL * 4 : 0; }

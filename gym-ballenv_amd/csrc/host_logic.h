@@ -164,7 +164,7 @@ inline const char* mlp_rollout_args_error(const void* obs_last, int32_t steps, c
   return nullptr;
 }
 
-// The optimiser arguments be_a2c_adam and be_mlp_opt share, checked in this order: the state, the Adam
+// The optimiser arguments be_a2c_adam, be_mlp_opt and be_cnn_adam share, checked in this order: the state, the Adam
 // constants (adam == false, plain SGD, has none), the loss log.  NULL: fine, else the message's tail,
 // which the entry point puts behind its own name.
 inline const char* optim_args_error(const double* state, bool adam, double beta1, double beta2, double eps,

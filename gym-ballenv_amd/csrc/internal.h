@@ -105,7 +105,7 @@ __attribute__((visibility("hidden"))) be_policy_view be_policy_get(const be_poli
 // caller has entered the policy's device.  BE_OK or an error code recorded in the ctx.
 __attribute__((visibility("hidden"))) int be_internal_policy_table(be_policy* pol, void* stream);
 
-// The state kernel behind an optimiser's update kernel (be_a2c_adam, be_mlp_opt; defined in a2c_adam.hip):
+// The state kernel behind an optimiser's update kernel (be_a2c_adam, be_mlp_opt, be_cnn_adam; defined in a2c_adam.hip):
 // one wave copies the `width` <= 64 losses into row (t mod log_rows) of loss_log (if there is one), then
 // advances state [t, beta1^t, beta2^t, lr] -- the step count alone unless `powers`.  One dim3(1), dim3(64)
 // launch on `stream`; the caller has checked the arguments and entered the device.  BE_OK or a HIP error

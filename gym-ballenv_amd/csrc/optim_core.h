@@ -1,9 +1,9 @@
-// optim_core.h -- the optimiser arithmetic include/ballenv.h pins, shared by the two update kernels
-// (a2c_adam_kernel in a2c_adam.hip, mlp_opt_kernel in mlp_policy.hip): one step's constants and one
+// optim_core.h -- the optimiser arithmetic include/ballenv.h pins, shared by the three update kernels
+// (a2c_adam_kernel in a2c_adam.hip, mlp_opt_kernel in mlp_policy.hip, cnn_adam_kernel in cnn_policy.hip): one step's constants and one
 // element's update.  f64 operations on f32 storage, no FMA (every unit is built with
 // -ffp-contract=off); the operand order below is the pinned one.
 // Reference: torch.optim.Adam (weight_decay=0, amsgrad=False, maximize=False), examples/ball_cnn_ac3.py:505,
-// examples/ball_env_reinforce.py:196; torch.optim.SGD (momentum=0), examples/train_supervise.py:75.
+// examples/ball_env_reinforce.py:196, examples/ball_cnn_reinforce.py:244; torch.optim.SGD (momentum=0), examples/train_supervise.py:75.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>

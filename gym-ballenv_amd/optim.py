@@ -1,10 +1,12 @@
 """What the on-GPU optimisers and gradient classes share.  ``HipOptim`` is the base of ``HipAdam`` (rollout.py:
-``be_a2c_adam`` on the six ``Policy`` tensors) and ``HipBlockOptim`` (block_policy.py: ``be_mlp_opt`` on the four
-or six ``BlockPolicy`` tensors).  Both C entries take the same arguments behind their handle -- params, grads and
+``be_a2c_adam`` on the six ``Policy`` tensors), ``HipBlockOptim`` (block_policy.py: ``be_mlp_opt`` on the four
+or six ``BlockPolicy`` tensors) and ``HipPixelAdam`` (pixel_policy.py: ``be_cnn_adam`` on the 14 ``PixelPolicy``
+parameters).  The C entries take the same arguments behind their handle -- params, grads and
 the two moments as tensor structs, the device state, the Adam constants, the losses and the loss log -- so
 everything but the names, shapes, struct and entry lives here: the tensor checks, ``step()`` up to the
 C call, the device state and learning rate, the loss-log ring and ``state_dict`` interchange with the torch
-optimisers.  ``RowGrad`` is the same for ``A2CGrad`` and ``BlockGrad`` (``be_a2c_grad``, ``be_mlp_grad``): the
+optimisers.  ``RowGrad`` is the same for ``A2CGrad``, ``BlockGrad`` and ``PixelGrad`` (``be_a2c_grad``, ``be_mlp_grad``,
+``be_cnn_grad``): the
 workspace, the gradient tensors, the checks of the weights and of the row tensors, and ``assign()``.  Also the
 helpers of that surface other classes use: ``is_f32`` (the weight check: ``_bind.fits`` for f32),
 ``unrolled_log`` and ``_beta_powers``.
@@ -56,12 +58,14 @@ class HipOptim:
     graph-captured; the learning rate lives on the device, so a captured step follows ``opt.lr = ...``.
 
     A subclass says what differs, as data: KINDS (kind -> the C arguments between the handle and the
-    tensor structs), LOSS_WIDTH, STRUCT (the ctypes tensor struct, six pointers: unused ones stay NULL),
+    tensor structs), LOSS_WIDTH, STRUCT (the ctypes tensor struct, SLOTS pointers -- six unless the subclass says
+    otherwise --: unused ones stay NULL),
     ON / MODULE (the messages' words for the policy handle and the module), and to ``__init__`` the entry
     and the parameters' names and shapes in the struct's order."""
 
     KINDS: dict = {}
     LOSS_WIDTH = 0
+    SLOTS = 6
     STRUCT = None
     ON = MODULE = ""
 
@@ -75,7 +79,7 @@ class HipOptim:
         self._lib, self._entry, self._lead = _abi.lib(), entry, self.KINDS[kind]
         dev = env.device
         self._names, self._name_set, self._shapes = tuple(names), frozenset(names), dict(zip(names, shapes))
-        self._pad = (None,) * (6 - len(self._names))
+        self._pad = (None,) * (self.SLOTS - len(self._names))
         self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
         if not (0.0 <= self.betas[0] < 1.0 and 0.0 <= self.betas[1] < 1.0) or self.eps < 0.0 or lr < 0.0:
             raise ValueError(f"{who} needs betas in [0, 1), eps >= 0 and lr >= 0")

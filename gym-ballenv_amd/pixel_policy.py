@@ -22,6 +22,9 @@ reference of the tests.
 recorded ``PixelRollout(record_images=True)``: gradients from torch autograd over the recorded images, or with
 grads="hip" from ``PixelGrad`` (``be_cnn_grad``, csrc/cnn_grad.hip: the loss and all 14 gradients straight from
 the u8 images, "sample" mode only -- the mode the reference trains in).
+``HipPixelAdam`` is ``optimizer.step()`` of that loop (``optim.Adam(lr=1e-3)``, :115, :244) fused with the re-pack
+of the weight image (``be_cnn_adam``); ``PixelTrainer`` is the training loop with no host round trip:
+rollout -> targets -> ``PixelGrad`` -> ``HipPixelAdam.step``, enqueued or graph-replayed.
 """
 from __future__ import annotations
 
@@ -36,8 +39,8 @@ import torch.nn.functional as F
 from . import _abi
 from ._bind import HipHandle, categorical_pick, golden, want
 from .block_policy import _episode_targets
-from .optim import RowGrad
-from .rollout import StepRollout, a2c_targets
+from .optim import HipOptim, RowGrad
+from .rollout import RolloutTrainer, StepRollout, a2c_targets
 
 # be_cnn_act's work split (csrc/cnn_host.h): a persistent grid of one workgroup per compute unit, WAVES waves
 # each, a workgroup taking TILE envs per round (tile t of G workgroups: workgroup t % G, round t // G)
@@ -273,6 +276,44 @@ class PixelGrad(RowGrad):
         return self._ran(rc, ws)
 
 
+class HipPixelAdam(HipOptim):
+    """``be_cnn_adam`` bound to one ``HipPixelPolicy`` and its ``PixelPolicy`` module: ``torch.optim.Adam``
+    (weight_decay=0, amsgrad=False, maximize=False -- ball_cnn_reinforce.py:115) on the 14 parameters in place
+    *and* the re-pack of the new weights into ``hip_pixel_policy``, in one asynchronous entry
+    (include/ballenv.h pins the arithmetic; reproducible bit for bit).  After ``step()``
+    ``policy.state_dict()`` is current and ``be_cnn_act`` runs the new weights: no ``HipPixelPolicy.load`` is
+    needed.  The BatchNorm running statistics are no parameters: the step leaves them, and their rows of the
+    weight image, as the last ``load`` wrote them.
+
+    Owns the moments (``exp_avg`` / ``exp_avg_sq``, keyed like ``policy.named_parameters()``, which is the
+    order of ``torch.optim.Adam(policy.parameters())``'s state), the device ``state`` [t, beta1^t, beta2^t, lr]
+    and, with ``log_rows`` > 0, a (log_rows, 2) f64 ``loss_log`` ring: the step that starts at count t copies
+    the ``losses`` it is given (the 2 f64 of ``PixelGrad.losses``) into row t % log_rows.  Nothing is allocated
+    per call and nothing synchronises, so a step can be graph-captured; the learning rate lives on the device,
+    so a captured step follows ``opt.lr = ...``.  eps must be > 0: ``PixelGrad``'s conv-bias gradients are exact
+    zeros, and 0 / (0 + eps) leaves those weights alone where 0 / 0 would make them NaN.  ``step``,
+    ``state_dict`` and the rest: ``HipOptim`` (optim.py)."""
+
+    KINDS = {"adam": ()}
+    LOSS_WIDTH = 2
+    SLOTS = len(_abi.CNN_PARAMS)
+    STRUCT = _abi.BeCnnTensors
+    ON, MODULE = "HipPixelPolicy", "a PixelPolicy module of the HipPixelPolicy's num_actions"
+
+    def __init__(self, hip_pixel_policy: HipPixelPolicy, policy: PixelPolicy, lr: float = 1e-3, betas=(0.9, 0.999),
+                 eps: float = 1e-8, log_rows: int = 0):
+        if float(eps) == 0.0:
+            raise ValueError("HipPixelAdam needs eps > 0 (the conv biases' gradients are exact zeros: 0 / 0)")
+        shapes = dict(PixelPolicy(hip_pixel_policy.num_actions).named_parameters())
+        super().__init__(hip_pixel_policy, policy, _abi.lib().be_cnn_adam, _abi.CNN_PARAMS,
+                         [tuple(shapes[k].shape) for k in _abi.CNN_PARAMS], "adam", lr, betas, eps, log_rows)
+
+    def load_state_dict(self, sd: dict) -> None:
+        if "eps" in sd["param_groups"][0] and float(sd["param_groups"][0]["eps"]) == 0.0:
+            raise ValueError("HipPixelAdam needs eps > 0 (the conv biases' gradients are exact zeros: 0 / 0)")
+        super().load_state_dict(sd)
+
+
 def pixel_reinforce_losses(policy: PixelPolicy, images: torch.Tensor, quadrants: torch.Tensor, actions: torch.Tensor,
                            rewards: torch.Tensor, dones: torch.Tensor, gamma: float = 0.99, targets=None) -> torch.Tensor:
     """Batched ``finish_episode`` (examples/ball_cnn_reinforce.py:98-117) over a recorded rollout:
@@ -309,7 +350,8 @@ def pixel_reinforce_update(rollout: PixelRollout, optimizer, gamma: float = 0.99
     (``rollout.hp.load``).  Returns the loss value.  grads: "torch" (``pixel_reinforce_losses`` + autograd)
     or "hip" (``PixelGrad``, cached on the rollout: the loss and every .grad from ``be_cnn_grad``, no autograd
     graph and no f32 copy of the images; needs targets="hip").  optimizer: a torch optimiser over
-    ``rollout.policy.parameters()``."""
+    ``rollout.policy.parameters()``, or with grads="hip" a ``HipPixelAdam`` bound to ``rollout.hp`` (the step reads
+    ``PixelGrad.grads`` directly and re-packs: no .grad copies, no load)."""
     if rollout.images is None:
         raise ValueError("pixel_reinforce_update needs PixelRollout(record_images=True)")
     if rollout.hp.norm != "sample":
@@ -318,6 +360,11 @@ def pixel_reinforce_update(rollout: PixelRollout, optimizer, gamma: float = 0.99
         raise ValueError("targets must be 'torch' or 'hip'")
     if grads not in ("torch", "hip"):
         raise ValueError("grads must be 'torch' or 'hip'")
+    hip_optim = isinstance(optimizer, HipPixelAdam)
+    if hip_optim and (optimizer.hp is not rollout.hp or optimizer.policy is not rollout.policy):
+        raise ValueError("the HipPixelAdam must be bound to this rollout's HipPixelPolicy and PixelPolicy")
+    if hip_optim and grads != "hip":
+        raise ValueError("a HipPixelAdam needs grads='hip'")
     if grads == "hip":
         if targets != "hip":
             raise ValueError("grads='hip' needs targets='hip'")
@@ -325,7 +372,10 @@ def pixel_reinforce_update(rollout: PixelRollout, optimizer, gamma: float = 0.99
         pg = getattr(rollout, "_pixel_grad", None)
         if pg is None or pg.policy is not rollout.policy:
             pg = rollout._pixel_grad = PixelGrad(rollout.env, rollout.policy)
-        pg(rollout.images, rollout.quadrants, rollout.actions, t.returns_norm, t.valid, scale=1.0)
+        g = pg(rollout.images, rollout.quadrants, rollout.actions, t.returns_norm, t.valid, scale=1.0)
+        if hip_optim:
+            optimizer.step(g, pg.losses)
+            return float(pg.losses[0])
         pg.assign()
         loss = float(pg.losses[0])
         optimizer.step()
@@ -342,3 +392,28 @@ def pixel_reinforce_update(rollout: PixelRollout, optimizer, gamma: float = 0.99
     optimizer.step()
     rollout.hp.load(rollout.policy)
     return float(loss.detach())
+
+
+class PixelTrainer(RolloutTrainer):
+    """The pixel agent's REINFORCE training loop (ball_cnn_reinforce.py:98-117, :244) with no host round
+    trip between two rollouts: per iteration ``PixelRollout`` -> ``a2c_targets_into`` (no values) ->
+    ``PixelGrad`` (scale 1) -> ``HipPixelAdam.step`` (which re-packs the policy), all enqueued on the caller's
+    current stream with nothing allocated and no synchronise.
+
+    Owns a ``PixelRollout(record_images=True, norm="sample")``, preallocated ``A2CTargets`` (returns_norm and
+    valid), a ``PixelGrad`` and a ``HipPixelAdam`` (``.opt``; ``log_rows`` sizes its loss log).  ``capture()``
+    records the rollout (``PixelRollout.capture``, ``chunk`` steps per graph) and the update half into HIP graphs,
+    linear chains on one stream, which ``train()`` then replays.  ``losses()``: the loss log as (iterations, 2)
+    f64 on the host -- the REINFORCE loss and the active rows of each iteration, the last ``log_rows`` of them
+    once the ring has wrapped (synchronises)."""
+
+    def __init__(self, env, policy: PixelPolicy, horizon: int, gamma: float = 0.99, lr: float = 1e-3,
+                 betas=(0.9, 0.999), eps: float = 1e-8, seed: int = 0x5E1EC7, log_rows: int = 0, chunk: int = 250):
+        super().__init__(env, policy, PixelRollout(env, policy, horizon, norm="sample", seed=seed, record_images=True),
+                         gamma)
+        self.chunk = self.GRAPH_CHUNK = int(chunk)
+        self.grad = PixelGrad(env, policy)
+        self.opt = HipPixelAdam(self.rollout.hp, policy, lr=lr, betas=betas, eps=eps, log_rows=log_rows)
+
+    def _grads(self, ro, tg):
+        return self.grad(ro.images, ro.quadrants, ro.actions, tg.returns_norm, tg.valid, scale=1.0), self.grad.losses

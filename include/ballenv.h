@@ -523,6 +523,42 @@ int be_cnn_grad(be_ctx* ctx, const uint8_t* images, const uint8_t* quadrants, co
  * One launch, asynchronous on stream, graph-capturable.                                            */
 int be_observe_quadrant(be_ctx* ctx, const be_state* st, uint8_t* out, void* stream);
 
+/* ---- the pixel agent's optimiser step and re-pack: optimizer.step() of examples/ball_cnn_reinforce.py ----
+ *   finish_episode       examples/ball_cnn_reinforce.py:115, :244   optim.Adam(policy.parameters(), lr=1e-3)
+ * One Adam step on the network's 14 parameters in place, and `cnn`'s packed image rebuilt from the new
+ * weights: afterwards the image holds exactly the bytes be_cnn_load would build from them and the running
+ * statistics that were last loaded, so be_cnn_act runs the updated network.  cnn's num_actions defines
+ * every shape (be_cnn_load's).  be_mlp_opt's contract (below) for this network, with one difference: the six
+ * running-statistics vectors are no parameters, so the step does not touch them -- their image rows and
+ * the image's pad and -inf entries keep what the last be_cnn_load wrote -- and a cnn that was never loaded
+ * is rejected.  (The reference's train-mode forward also updates running_mean / running_var, which it
+ * never reads: policy.eval() is never called.  Maintaining them is not part of this entry.)
+ * All tensors are contiguous f32 device arrays in state_dict layout: params (updated), grads (read: what
+ * be_cnn_grad writes), exp_avg and exp_avg_sq (updated; zeros for a fresh optimiser).
+ * state: 4 f64 on the device, [t, beta1^t, beta2^t, lr], as be_mlp_opt's; a fresh optimiser holds
+ * [0, 1, 1, lr].  The arithmetic is BE_MLP_OPT_ADAM's, pinned below: every operation one f64 operation, no
+ * FMA.  Every element is computed from the state as it was before the call; the state advances exactly
+ * once per call, after all of them.  be_cnn_grad's conv*_bias gradients are exact +0: with eps > 0 the
+ * pinned arithmetic then leaves those weights and their moments bit-unchanged (m' = v' = 0,
+ * w' = w - ss * (0 / eps)); with eps = 0 it is 0 / 0.  They are not treated specially.
+ * losses / loss_log: both NULL, or losses = the 2 f64 of be_cnn_grads.losses and loss_log a
+ * (log_rows, 2) f64 device array, log_rows >= 1: row (t mod log_rows) receives a copy of losses, t
+ * being the state's step count before the call -- a replayed graph logs every iteration's losses.
+ * Asynchronous on `stream`, no allocation and no synchronisation (graph-capturable as a linear
+ * chain); two launches: the update + pack kernel, the state kernel.
+ * BE_E_INVALID, with nothing launched: a NULL cnn; a cnn never loaded ("be_cnn_adam before be_cnn_load");
+ * a NULL set; a NULL or not 4-byte aligned tensor, named in the message ("grads->conv2_weight"); state
+ * NULL or not 8-byte aligned; a beta outside [0, 1) or eps < 0; losses and loss_log not both or neither,
+ * or not 8-byte aligned; log_rows < 1 with a log.                                                   */
+typedef struct be_cnn_tensors {     /* f32 device arrays, state_dict shapes: the 14 parameters in be_cnn_grads' order */
+  float *conv1_weight, *conv1_bias, *bn1_weight, *bn1_bias, *conv2_weight, *conv2_bias, *bn2_weight, *bn2_bias,
+        *conv3_weight, *conv3_bias, *bn3_weight, *bn3_bias, *head_weight, *head_bias;
+} be_cnn_tensors;
+int be_cnn_adam(be_cnn* cnn, const be_cnn_tensors* params, const be_cnn_tensors* grads,
+                const be_cnn_tensors* exp_avg, const be_cnn_tensors* exp_avg_sq, double* state,
+                double beta1, double beta2, double eps,
+                const double* losses, double* loss_log, int32_t log_rows, void* stream);
+
 /* ---- the block-count MLP's losses and gradients: both of the reference's training loops ----
  *   finish_episode       examples/ball_env_reinforce.py:88-108  sum of -Categorical(probs).log_prob(a) * R^
  *   the supervised loop  examples/train_supervise.py:66-101     mean CrossEntropyLoss on the logits
